@@ -23,13 +23,23 @@ stream k codes clip k mod 8):
 The legs are frame-pipelined: the host parse, upload and GPU reconstruction
 of frame i run while the GPU encodes frame i + 1.  value = K x W x H x frames
 / wall time of the step (input upload, both legs, host parse and the H2D of
-its output all included).  One extra step runs the legs one after the other
-to report their split (config.serial_*).
+its output all included).
 
-Reported beside it (not part of `value`): the single-stream enc+dec latency,
-decode_only (the reconstruction of resident parse output, the round-1
-figure), the k_recon roofline (the north-star 4K inter-reconstruction kernel,
-hipEvents on its stream) and a few kernel legs.
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what that
+figure needs: set-up, the warm-up steps, the N timed steps, one check of the
+last timed step (every stream's .bit against the reference Thorenc's, one
+stream per clip decoded against the reference Thordec's) and the JSON line.
+`--dump-outputs DIR` also writes what the last timed step returned (DIR/*.npy,
+see dump_outputs).
+
+`--full` adds everything else, reported beside `value` and not part of it:
+the full check of the timed steps (every stream's decoded sequence), one
+extra step with the legs one after the other (config.serial_*), the
+single-stream enc+dec latency, decode_only (the reconstruction of resident
+parse output, the round-1 figure), the k_recon roofline (the north-star 4K
+inter-reconstruction kernel, hipEvents on its stream), the config-4 row split
+(`rows`), a few kernel legs, the config-3 / config-5 encoder legs and the
+reference's CPU baseline.
 
 N > 1: one process per GPU, each with its own K streams (no data-path
 collective): scaling "weak"; `bench.py --gpus N` run directly starts the N
@@ -754,6 +764,49 @@ def rows_guarded(a, torch, dist, rank, world, local, out):
         tm.cancel()
 
 
+FULL_CHECK_STEPS = 4  # --full: timed steps whose every decoded stream is read back and checked (first 3 + last)
+DUMP_STREAMS = 8  # --dump-outputs: streams whose decoded frames are sampled
+DUMP_POSITIONS = 1 << 16  # ... byte positions sampled in each of their I420 frames
+DUMP_BIT_BYTES = 1 << 17  # ... leading .bit bytes kept per clip
+DUMP_SEED = 20240607
+
+
+def dump_outputs(path: str, bits, decs, nf: int, fsize: int, leaders) -> None:
+    """--dump-outputs DIR: what the last timed step handed back -- every
+    stream's .bit (bits[k]) and its decoded frames (resident in decs[k]) -- as
+    DIR/<name>.npy, about 21 MB in all.  The streams and byte positions sampled
+    come from a fixed seed, so two runs with the same arguments write arrays
+    that can be compared element for element:
+      bitstream_digest.npy  float64 [K, 2]   every stream's .bit length, CRC-32
+      bitstream_head.npy    float32 [clips, DUMP_BIT_BYTES]   the leading bytes of
+                            the .bit of each clip's first stream (zero padded)
+      decoded_streams.npy   float64 [S]      the S = min(K, DUMP_STREAMS) sampled stream indices
+      decoded_digest.npy    float64 [S, nf]  CRC-32 of each of their I420 frames
+      decoded_sample.npy    float32 [S, nf, DUMP_POSITIONS]   the frame bytes at
+                            the sampled positions"""
+    import zlib
+
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    ks = np.sort(rng.choice(len(decs), min(len(decs), DUMP_STREAMS), replace=False))
+    pos = np.sort(rng.integers(0, fsize, DUMP_POSITIONS))
+    digest = np.array([[len(b), zlib.crc32(b)] for b in bits], np.float64)
+    head = np.zeros((len(leaders), DUMP_BIT_BYTES), np.float32)
+    for j, k in enumerate(leaders):
+        b = np.frombuffer(bits[k][:DUMP_BIT_BYTES], np.uint8)
+        head[j, :len(b)] = b
+    fdig = np.zeros((len(ks), nf), np.float64)
+    samp = np.zeros((len(ks), nf, DUMP_POSITIONS), np.float32)
+    for j, k in enumerate(ks):
+        for i in range(nf):
+            fr = decs[k].read_i420(i)
+            fdig[j, i] = zlib.crc32(fr)
+            samp[j, i] = np.frombuffer(fr, np.uint8)[pos]
+    for name, arr in (("bitstream_digest", digest), ("bitstream_head", head), ("decoded_streams", ks.astype(np.float64)),
+                      ("decoded_digest", fdig), ("decoded_sample", samp)):
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
 def launch_ranks(n: int) -> int:
     """bench.py --gpus N run directly (no torch.distributed.run): start N ranks
     of this script, one per GPU, before anything here touches a GPU, with the
@@ -803,6 +856,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also everything reported beside `value`: the full check of every stream's decoded frames, "
+                         "the serial step, latency, decode_only, roofline, rows, kernel and encoder legs, CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--config3-streams", type=int, default=128,
                     help="streams of the BASELINE config-3 encoder leg (1080p LDB high efficiency)")
@@ -840,6 +898,8 @@ def main():
     ap.add_argument("--rows-passes", type=int, default=5, help="timed passes of the row-split leg's 8-frame stream")
     ap.add_argument("--launcher-selftest", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1 (the number of timed steps)")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:  # not under torch.distributed.run: be the launcher
         sys.exit(launch_ranks(a.gpus))
@@ -858,7 +918,7 @@ def main():
 
     clips = None
     cfg5 = None
-    if a.shard == "streams" and world == 1 and not a.no_legs and a.config5_streams > 0:
+    if a.full and a.shard == "streams" and world == 1 and not a.no_legs and a.config5_streams > 0:
         cfg5 = config5_frames()  # before anything touches the GPU (worker processes fork)
         progress("config-5 input synthesised")
     if a.shard == "streams":  # synthesise the inputs before anything touches the GPU (worker processes fork)
@@ -1089,11 +1149,14 @@ def main():
         return ok
 
     allk = list(range(K))
+    leaders = [clip_of.index(c) for c in sorted(set(clip_of))]  # the first stream of each clip
     progress("%d encoder + decoder contexts ready" % K)
     for _ in range(max(1, a.warmup)):
         _, bits, devs = step_pipe(allk)
         progress("warmup step done")
-    bit_exact = bits_ok(allk, bits) and decoded_ok(allk)
+    bit_exact = True
+    if a.full:
+        bit_exact = bits_ok(allk, bits) and decoded_ok(allk)
     rf_early = None
     if os.environ.get("THOR_BENCH_RF_EARLY"):  # diagnostic: the roofline pass before the timed steps too
         _, rf_early, _, _, _ = roofline_pass(lib, decs, [groups[0]], devs, [parse_stream(bits[k])[1] for k in groups[0]],
@@ -1103,59 +1166,71 @@ def main():
         dist.barrier()
     torch.cuda.synchronize(local)
     elapsed = 0.0
-    for _ in range(a.steps):
+    for s in range(a.steps):
         te, bits, devs = step_pipe(allk)
         elapsed += te
         progress("timed step: %.1f ms" % (te * 1e3))
-        bit_exact &= bits_ok(allk, bits)
-        bit_exact &= decoded_ok(allk)  # every timed step's decode checked too (outside the timed region)
+        # checked outside the timed region.  A plain run checks its last step only: every .bit, and the
+        # decoded sequence of one stream per clip.  --full: every stream's decoded sequence too, on the
+        # first steps and the last one (FULL_CHECK_STEPS in all: reading 240 decoded streams back takes
+        # several times a step's own time)
+        last = s == a.steps - 1
+        if a.full and (last or s < FULL_CHECK_STEPS - 1):
+            bit_exact &= bits_ok(allk, bits)
+            bit_exact &= decoded_ok(allk)
+        elif a.full or last:
+            bit_exact &= bits_ok(allk, bits)
+            bit_exact &= decoded_ok(leaders)
     torch.cuda.synchronize(local)
+    if a.dump_outputs and rank == 0:  # before anything below runs the contexts again
+        dump_outputs(a.dump_outputs, bits, decs, nf, fsize, leaders)
+        progress("outputs of the last timed step written")
     if dist is not None:
         dist.barrier()
-    # the two legs one after the other (one untimed-for-value step): the split of the work
-    dec_host_s[0] = 0.0
-    t_enc, t_dec, bits, devs, fms = step(allk)
-    progress("serial step done")
-    bit_exact &= bits_ok(allk, bits)
-    enc_frame_ms = fms
-    dec_host_ms = dec_host_s[0] * 1e3
     elapsed = reduce_max(dist, dev, elapsed)
-    bit_exact = -reduce_max(dist, dev, -1.0 if bit_exact else 0.0) == 1.0
     px_stream = W * H * nf
     value = world * K * px_stream * a.steps / elapsed / 1e6
     in_bytes = K * nf * fsize
 
-    # ---- beside `value` ----
-    # single-stream latency: stream 0 alone, encode (its input upload included) + decode
-    lat = [step([0])[:2] for _ in range(2)]
-    lat_enc, lat_dec = min(x[0] for x in lat), min(x[1] for x in lat)
-    # decode_only: reconstruction of every stream's resident parse output (no parse, no upload)
-    dsteps = 5
-    for k in allk:
-        decs[k].sync()
-    t0 = time.perf_counter()
-    for _ in range(dsteps):
-        for i in range(nf):
-            for gk in groups:
-                decode_batch([decs[k] for k in gk], [devs[k][i] for k in gk])
-    for k in allk:
-        decs[k].sync()
-    t_do = (time.perf_counter() - t0) / dsteps
-    frames_of = [parse_stream(bits[k])[1] for k in groups[0]]
-    progress("roofline pass")
-    stage_ms, recon_ms, alg, B, prep_ms = roofline_pass(lib, decs, [groups[0]], devs, frames_of, seq, 3)
-    achieved = alg / (recon_ms / 1e3) / 1e9 if recon_ms > 0 else 0.0
-    path_ms = prep_ms + recon_ms
-    path_achieved = alg / (path_ms / 1e3) / 1e9 if path_ms > 0 else 0.0
-    traffic = None
-    traffic_source = None
-    tj = a.traffic_json or os.path.join(ROOT, "tools", "traffic_latest.json")
-    if os.path.exists(tj):
-        tjd = json.load(open(tj))
-        traffic = tjd.get("recon_hbm_bytes_per_p_launch")
-        # the PMC passes this static figure came from: their profile tag and the commit of the kernels measured
-        traffic_source = {"file": os.path.relpath(tj, ROOT), "profile_tag": tjd.get("tag"),
-                          "kernels_commit": tjd.get("commit"), "profile": tjd.get("profile")}
+    if a.full:  # ---- beside `value` ----
+        # the two legs one after the other (one untimed-for-value step): the split of the work
+        dec_host_s[0] = 0.0
+        t_enc, t_dec, bits, devs, fms = step(allk)
+        progress("serial step done")
+        bit_exact &= bits_ok(allk, bits)
+        enc_frame_ms = fms
+        dec_host_ms = dec_host_s[0] * 1e3
+        # single-stream latency: stream 0 alone, encode (its input upload included) + decode
+        lat = [step([0])[:2] for _ in range(2)]
+        lat_enc, lat_dec = min(x[0] for x in lat), min(x[1] for x in lat)
+        # decode_only: reconstruction of every stream's resident parse output (no parse, no upload)
+        dsteps = 5
+        for k in allk:
+            decs[k].sync()
+        t0 = time.perf_counter()
+        for _ in range(dsteps):
+            for i in range(nf):
+                for gk in groups:
+                    decode_batch([decs[k] for k in gk], [devs[k][i] for k in gk])
+        for k in allk:
+            decs[k].sync()
+        t_do = (time.perf_counter() - t0) / dsteps
+        frames_of = [parse_stream(bits[k])[1] for k in groups[0]]
+        progress("roofline pass")
+        stage_ms, recon_ms, alg, B, prep_ms = roofline_pass(lib, decs, [groups[0]], devs, frames_of, seq, 3)
+        achieved = alg / (recon_ms / 1e3) / 1e9 if recon_ms > 0 else 0.0
+        path_ms = prep_ms + recon_ms
+        path_achieved = alg / (path_ms / 1e3) / 1e9 if path_ms > 0 else 0.0
+        traffic = None
+        traffic_source = None
+        tj = a.traffic_json or os.path.join(ROOT, "tools", "traffic_latest.json")
+        if os.path.exists(tj):
+            tjd = json.load(open(tj))
+            traffic = tjd.get("recon_hbm_bytes_per_p_launch")
+            # the PMC passes this static figure came from: their profile tag and the commit of the kernels measured
+            traffic_source = {"file": os.path.relpath(tj, ROOT), "profile_tag": tjd.get("tag"),
+                              "kernels_commit": tjd.get("commit"), "profile": tjd.get("profile")}
+    bit_exact = -reduce_max(dist, dev, -1.0 if bit_exact else 0.0) == 1.0
 
     out = None
     if rank == 0:
@@ -1176,8 +1251,15 @@ def main():
                     "region (H2D on a copy stream, overlapped with encoding); decoded frames stay in HBM"
                     % (nclip, [c["seed"] for c in clips_meta]),
             "bit_exact": bit_exact,
-            "bit_exact_scope": "every stream of every timed step: .bit md5 == the reference Thorenc's for its clip, "
-                               "decoded sequence == the reference Thordec's (tests/golden/bench_clips.json)",
+            "bit_exact_scope": (
+                "every stream of every timed step: .bit md5 == the reference Thorenc's for its clip; decoded sequence "
+                "== the reference Thordec's (tests/golden/bench_clips.json) for every stream of the warm-up, the "
+                "first %d and the last timed step, for one stream per clip of the others" % (FULL_CHECK_STEPS - 1)
+                if a.full else
+                "the last timed step: every stream's .bit md5 == the reference Thorenc's for its clip, the decoded "
+                "sequence of one stream per clip == the reference Thordec's (tests/golden/bench_clips.json); --full "
+                "checks every stream's decoded sequence"),
+            "full": a.full,
             "config": {
                 "workload": "encode + decode of 4K (3840x2160) 8-frame config_LDB_low_complexity streams: "
                             "raw frames host -> HBM, device-resident encoder (RD loop, loop filters, CLPF, bit "
@@ -1191,6 +1273,13 @@ def main():
                               "GPU reconstruction of frame i run while the GPU encodes frame i + 1 (value = wall "
                               "time of everything complete)",
                 "pipe_timeline_last_step": pipe_tl,
+                "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
+                "decoder_stream_priority": "high" if a.dec_priority else "default",
+                "enc_cu_exclude_per_32": a.enc_cu_exclude,
+            },
+        }
+        if a.full:
+            out["config"].update({
                 "serial_t_enc_ms": round(t_enc * 1e3, 2),
                 "serial_t_dec_ms": round(t_dec * 1e3, 2),
                 "serial_mpx_s": round(K * px_stream / (t_enc + t_dec) / 1e6, 2),
@@ -1209,11 +1298,8 @@ def main():
                 "decode_only_note": "GPU reconstruction of the K streams' resident parse output (no parse, "
                                     "no upload): the round-1 headline",
                 "stage_ms_per_stream_pass": {k: round(v, 4) for k, v in zip(STAGES + ["interp"], stage_ms)},
-                "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
-                "decoder_stream_priority": "high" if a.dec_priority else "default",
-                "enc_cu_exclude_per_32": a.enc_cu_exclude,
-            },
-            "roofline": {
+            })
+            out["roofline"] = {
                 "bound": "hbm",
                 "kernel": "k_recon",
                 "achieved": round(achieved, 1),
@@ -1244,14 +1330,15 @@ def main():
                                         "integer RD search with negligible HBM traffic and no MFMA work, latency "
                                         "bound inside the wave (DESIGN.md 3b), so neither roofline bounds it; this "
                                         "object is k_recon, the north star's inter-reconstruction kernel",
-            },
-        }
-    if not a.no_rows:  # every rank: the north star's row split of ONE config-4 stream at this N
+            }
+    if a.full and not a.no_rows:  # every rank: the north star's row split of ONE config-4 stream at this N
         progress("rows leg: config 4 over %d rank(s)" % world)
         rows = rows_guarded(a, torch, dist, rank, world, local, out)
         if rank == 0:
             out["rows"] = rows
-    if rank == 0:
+    if rank == 0 and not a.full:
+        print(json.dumps(out), flush=True)
+    elif rank == 0:
         if world == 1 and not a.no_legs:
             progress("legs")
             out["encoder_tu_chain"] = encoder_leg(torch, lib)

@@ -56,7 +56,7 @@ def main():
     rows = kernel_stats(os.path.join(d, "trace", "run_results.db"))
     lines = ["# rocprofv3 --kernel-trace --stats  (%s)" % tag,
              "# command: rocprofv3 --kernel-trace --stats -- " + (sys.argv[3] if len(sys.argv) > 3 else
-                                                                   "python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline"),
+                                                                   "python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline"),
              "# (averages below mix the concurrent multi-stream timed region and the single-stream passes)",
              "%-24s %8s %14s %12s %8s" % ("kernel", "calls", "total_us", "avg_us", "pct")]
     for name, calls, tot, avg, pct in rows:
