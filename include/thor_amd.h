@@ -453,6 +453,10 @@ int thor_enc_seq_profile(thor_enc_t *e0, long long *out, int n);
  * summed over its workers (100 MHz ticks): time coding superblocks, time
  * waiting for a queue slot, superblocks coded; cleared.  Returns 3. */
 int thor_enc_rows_profile(int device, long long *out);
+/* 8x8 CUs of I frames that kernel coded through its register-resident leaf
+ * path (THOR_ENC_LEAF8, default on) on `device` since the last call or the
+ * last thor_enc_rows_profile; cleared.  Negative: a THOR_ERR_* code. */
+long long thor_enc_leaf8_count(int device);
 /* The last coded frame's reconstruction (deblocked, CLPF'd), host planes. */
 int thor_enc_read_recon(thor_enc_t *e, uint8_t *y, uint8_t *u, uint8_t *v);
 /* Per-superblock RD costs (parity instrumentation, tests/golden/rd_costs.npz):

@@ -160,7 +160,8 @@ __device__ __forceinline__ void te_sb_cellinfo(const TeJob &J, int k, int l) {
 }
 
 // k_enc_rows' profile, summed over its workers across launches (100 MHz ticks): time coding SBs,
-// time waiting for a queue slot, SBs coded (thor_enc_rows_profile reads and clears it)
+// time waiting for a queue slot, SBs coded (thor_enc_rows_profile reads and clears it); [3]: CUs coded
+// by te_leaf8_intra (thor_enc_leaf8_count)
 __device__ unsigned long long g_te_rows_prof[4];
 __global__ __launch_bounds__(64) TE_WPE void k_enc_rows(const TeJob *__restrict__ jobs, unsigned total, unsigned *q,
                                                  unsigned *items, TeScratchMem *scratch, unsigned *err,
@@ -170,6 +171,7 @@ __global__ __launch_bounds__(64) TE_WPE void k_enc_rows(const TeJob *__restrict_
   // the worker's buffers (te_here): LDS at fixed addresses (g_te_*), global at
   // fixed offsets from its TeScratchMem
   g_te_mem = &scratch[blockIdx.x];
+  if (threadIdx.x == 0) g_te_leaf8_n = 0u;
   te_load_basis(g_te_tx);
   te_load_zig();
   TeSB &sb = s_sb;
@@ -336,6 +338,7 @@ __global__ __launch_bounds__(64) TE_WPE void k_enc_rows(const TeJob *__restrict_
     atomicAdd(&g_te_rows_prof[0], t_work);
     atomicAdd(&g_te_rows_prof[1], t_wait);
     atomicAdd(&g_te_rows_prof[2], n_sb);
+    if (g_te_leaf8_n) atomicAdd(&g_te_rows_prof[3], (unsigned long long)g_te_leaf8_n);
   }
 }
 
@@ -1007,6 +1010,16 @@ int thor_enc_set_cu_mask(thor_enc_t *e, const uint32_t *mask, int nwords) {
   return THOR_OK;
 }
 
+// THOR_ENC_LEAF8=0 in the environment (read once): I-frame 8x8 CUs keep the generic candidate path
+// instead of te_leaf8_intra -- the A/B switch of one binary, and the tests' handle on both paths.
+static int enc_leaf8_on() {
+  static const int on = [] {
+    const char *v = getenv("THOR_ENC_LEAF8");
+    return !(v && v[0] == '0' && v[1] == 0);
+  }();
+  return on;
+}
+
 // One context's frame job.  Its device setup (cells, SB dependency counters,
 // scheduler queue: k_enc_clear) runs on the batch stream `st`; its header words go to `hw` (host), which
 // the caller uploads with every context's in one copy to `hdr_dev`.
@@ -1076,6 +1089,7 @@ static int enc_prepare(thor_enc *e, const uint8_t *orig, int orig_stride, TeJob 
   F.sync = P.sync;
   F.early_skip_thr = P.early_skip_thr;
   F.es_thr = e->es_thr;
+  F.leaf8 = enc_leaf8_on();
   J.sb_words = e->sb_words;
   J.sb_nbits = e->sb_nbits;
   J.deps = e->deps;
@@ -1433,6 +1447,17 @@ int thor_enc_rows_profile(int device, long long *out) {
   EHIP(hipMemcpyToSymbol(HIP_SYMBOL(g_te_rows_prof), z, sizeof(z)));
   for (int i = 0; out && i < 3; i++) out[i] = (long long)v[i];
   return 3;
+}
+
+// CUs k_enc_rows coded through te_leaf8_intra on `device` since the last call (or the last
+// thor_enc_rows_profile); cleared.
+long long thor_enc_leaf8_count(int device) {
+  unsigned long long v = 0, z = 0;
+  EHIP(hipSetDevice(device));
+  EHIP(hipDeviceSynchronize());
+  EHIP(hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_te_rows_prof), sizeof(v), 3 * sizeof(v)));
+  EHIP(hipMemcpyToSymbol(HIP_SYMBOL(g_te_rows_prof), &z, sizeof(z), 3 * sizeof(z)));
+  return (long long)v;
 }
 
 int thor_enc_frame(thor_enc_t *e, const uint8_t *orig, int orig_stride) {

@@ -249,7 +249,7 @@ __device__ __forceinline__ void te_trace_put(int fr, int k, int y, int x, int a,
 
 enum { TP_WCOEF, TP_WBLOCK, TP_INTER_COMP, TP_INTRA_COMP, TP_ENC_BLOCK, TP_COST, TP_SEARCH_INTRA, TP_ME, TP_MODE,
        TP_ES_CHECK, TP_ES_SEARCH, TP_COMMIT, TP_MC_Y, TP_MC_C, TP_FWD, TP_QUANT, TP_INV, TP_IPRED, TP_TOPLEFT, TP_SAD,
-       TP_SB, TP_WAIT, TP_N };
+       TP_SB, TP_WAIT, TP_LEAF8, TP_LEAF8_SEARCH, TP_LEAF8_CHAINS, TP_LEAF8_SYNTAX, TP_LEAF8_COMMIT, TP_N };
 
 #define TE_MIN(a, b) ((a) < (b) ? (a) : (b))
 #define TE_MAX(a, b) ((a) > (b) ? (a) : (b))
@@ -320,6 +320,7 @@ struct TeFrame {
   int speed, enable_tb_split, enable_pb_split, enable_bipred, max_delta_qp, delta_qp_step;
   int intra_rdo, use_block_contexts, rdoq, sync;
   float early_skip_thr;
+  int leaf8;          // device: I-frame 8x8 CUs take te_leaf8_intra (THOR_ENC_LEAF8, default on); fills the padding
   const int *es_thr;  // early-skip thresholds [2][52][4], te_es_thresholds (host)
 };
 
@@ -897,7 +898,8 @@ TE_FN void te_coeff_events(TeBits &b, const TeScanRegs &R, int N, int size, int 
 // The writer state travels by value (in registers) in and out: a reference
 // would pin the caller's register copy to the stack.  Inlined into
 // write_block (its only caller): no call frame per coded TU.
-TE_FN TeBits te_write_coeff(TeBits b_in, const int16_t *c, int size, int type) {
+// te_write_coeff_scan: the coder on scan-order levels already in registers.
+TE_FN TeBits te_write_coeff_scan(TeBits b_in, const TeScanRegs &R, int size, int type) {
   TE_P(TP_WCOEF);
   TeBits b = te_bits_local(b_in);
   size = te_uni(size);
@@ -905,8 +907,6 @@ TE_FN TeBits te_write_coeff(TeBits b_in, const int16_t *c, int size, int type) {
   const int q = TE_MIN(16, size), N = q * q;
   const int chroma = type & 1, intra = (type >> 1) & 1;
   int vlc_adaptive = intra && !chroma;
-  TeScanRegs R;
-  te_load_scan(R, c, q);
   int last_pos = R.last_nz();
   if (last_pos < 0) last_pos = 0;  // cbp != 0 guarantees a non-zero level (fatalerror otherwise, :142-143)
   int pos = 0;
@@ -974,6 +974,11 @@ TE_FN TeBits te_write_coeff(TeBits b_in, const int16_t *c, int size, int type) {
     }
   }
   return b;
+}
+TE_FN TeBits te_write_coeff(TeBits b_in, const int16_t *c, int size, int type) {
+  TeScanRegs R;
+  te_load_scan(R, c, TE_MIN(16, te_uni(size)));
+  return te_write_coeff_scan(b_in, R, size, type);
 }
 
 // write_block's code tables (enc/write_bits.c:385 cbp codes, :401-413 intra mode codes),

@@ -487,13 +487,15 @@ TE_FN uint32_t te_or16(uint32_t v) {  // OR over lanes 0..15 (lanes >= 16 contri
 }
 // residual -> levels (into coef) -> reconstruction (into rec, stride 4) of the
 // 4 x 4 block whose prediction lane r < 16 holds in p; returns cbp
-TE_FN int te_c4_code(int p, const uint8_t *org, int os, int qp, int16_t *coef, uint8_t *rec, int type) {
+// te_c4_core: the chain on registers -- o: the original pixel of lane r < 16;
+// lev_out / v_out: its level and reconstructed pixel (what te_c4_code stores)
+TE_FN int te_c4_core(int p, int o, int qp, int type, int &lev_out, int &v_out) {
   const int lane = TE_LANE, r = lane & 15, i = r >> 2, j = r & 3, base = lane & ~15;
   const bool act = lane < 16;
   // HEVC 4-point basis rows (D[i][k]) and columns (D[k][j]) as packed int8
   const uint32_t rowD = i == 0 ? 0x40404040u : (i == 1 ? 0xADDC2453u : (i == 2 ? 0x40C0C040u : 0xDC53AD24u));
   const uint32_t colD = j == 0 ? 0x24405340u : (j == 1 ? 0xADC02440u : (j == 2 ? 0x53C0DC40u : 0xDC40AD40u));
-  const int R = (int)org[i * os + j] - p;
+  const int R = o - p;
   // transform (common/transform.c:309-327): T = D R^T, C = D T^T, 16-bit wraps; N = 4: shifts 2, 7
   int t = 0;
 #pragma unroll
@@ -558,7 +560,7 @@ TE_FN int te_c4_code(int p, const uint8_t *org, int os, int qp, int16_t *coef, u
     }
     if ((chg >> pos) & 1) lev = ((neg >> pos) & 1) ? -1 : 1;
   }
-  if (act) coef[r] = (int16_t)lev;
+  lev_out = lev;
   int v = p;
   if (cbp) {
     // dequantize (common/common_block.c:132-146): rshift 1, add 1
@@ -574,7 +576,17 @@ TE_FN int te_c4_code(int p, const uint8_t *org, int os, int qp, int16_t *coef, u
     res = te_clip16((res + 2048) >> 12);
     v = te_clip255(res + p);
   }
-  if (act) rec[r] = (uint8_t)v;
+  v_out = v;
+  return cbp;
+}
+TE_FN int te_c4_code(int p, const uint8_t *org, int os, int qp, int16_t *coef, uint8_t *rec, int type) {
+  const int r = TE_LANE & 15;
+  int lev, v;
+  const int cbp = te_c4_core(p, (int)org[(r >> 2) * os + (r & 3)], qp, type, lev, v);
+  if (TE_LANE < 16) {
+    coef[r] = (int16_t)lev;
+    rec[r] = (uint8_t)v;
+  }
   te_sync();
   return cbp;
 }
@@ -612,11 +624,13 @@ TE_FN int te_fwd8r(const int *s, int k, int shift) {  // te_fwd8 (enc_pix.h) on 
   }
   return te_wrap16((v + (1 << (shift - 1))) >> shift);
 }
-TE_FN int te_c8_code(int p, const uint8_t *org, int os, int qp, int16_t *coef, uint8_t *rec, int type) {
+// te_c8_core: the chain on registers (o: lane r's original pixel; lev_out /
+// v_out: its level and reconstructed pixel, what te_c8_code stores)
+TE_FN int te_c8_core(int p, int o, int qp, int type, int &lev_out, int &v_out) {
   const TeScratch S = te_here();
   const TeTx &X = *S.tx;
   const int L = TE_LANE, hi = L >> 3, lo = L & 7;
-  const int R = (int)org[hi * os + lo] - p;
+  const int R = o - p;
   // transform8 (common/common_kernels.c:1887-1967): T[k][row] from row `row` of R, then C[k][row] from row `row` of T
   int x[8];
 #pragma unroll
@@ -682,7 +696,7 @@ TE_FN int te_c8_code(int p, const uint8_t *org, int os, int qp, int16_t *coef, u
     }
     if ((chg >> pos) & 1) lev = ((neg >> pos) & 1) ? -1 : 1;
   }
-  coef[L] = (int16_t)lev;
+  lev_out = lev;
   int v = p;
   if (cbp) {
     // dequantize (common/common_block.c:132-146): rshift 2, add 2
@@ -701,6 +715,14 @@ TE_FN int te_c8_code(int p, const uint8_t *org, int os, int qp, int16_t *coef, u
     res = te_clip16((res + 2048) >> 12);
     v = te_clip255(res + p);
   }
+  v_out = v;
+  return cbp;
+}
+TE_FN int te_c8_code(int p, const uint8_t *org, int os, int qp, int16_t *coef, uint8_t *rec, int type) {
+  const int L = TE_LANE;
+  int lev, v;
+  const int cbp = te_c8_core(p, (int)org[(L >> 3) * os + (L & 7)], qp, type, lev, v);
+  coef[L] = (int16_t)lev;
   rec[L] = (uint8_t)v;
   te_sync();
   return cbp;
@@ -1016,6 +1038,33 @@ TE_FN void te_isearch(const TeNbr &nb, const TeIpc &c, const uint8_t *o, int os,
     }
   }
 }
+// 8 x 8: four modes per pass, one per 16-lane row -- lane ch = lane & 15 of each
+// row holds the original's four pixels (ch >> 1, 4 (ch & 1) ..) in org; a row's
+// SAD is one DPP reduction
+TE_FN void te_isearch8(const TeNbr &nb, const TeIpc &c, uint32_t org, const int8_t *order, int n, int &min_sad,
+                       int &best) {
+  const int ch = TE_LANE & 15, row = TE_LANE >> 4, i = ch >> 1, j = (ch & 1) * 4;
+#pragma unroll
+  for (int pass = 0; pass < 3; pass++) {
+    if (4 * pass >= n) break;
+    const int k = 4 * pass + row;
+    uint32_t a = 0;
+    if (k < n) a = te_sad4(org, te_ipx4(nb, c, 8, order[k], i, j), 0);
+    a += (uint32_t)TE_DPP(a, 0xB1);
+    a += (uint32_t)TE_DPP(a, 0x4E);
+    a += (uint32_t)TE_DPP(a, 0x141);
+    a += (uint32_t)TE_DPP(a, 0x140);
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int kk = 4 * pass + r;
+      const int sad = __builtin_amdgcn_readlane((int)a, 16 * r);
+      if (kk < n && sad < min_sad) {
+        best = order[kk];
+        min_sad = sad;
+      }
+    }
+  }
+}
 #endif
 
 // search_intra_prediction_params, enc/encode_block.c:1230-1329: SAD over the
@@ -1043,28 +1092,8 @@ TE_NOINL int te_search_intra(const TeFrame &F_, const TeBlockInfo &bi_, int num_
   if (TE_LANE == 0) g_te_nb_key = te_nb_key(ypos, xpos, size);  // (te_intra_pred below forgets it, sizes 32 / 64)
   te_sync();
   if (size == 8) {
-    const int ch = TE_LANE & 15, row = TE_LANE >> 4, i = ch >> 1, j = (ch & 1) * 4;
-    const uint32_t org = te_ld4(o + i * F.osy + j);
-#pragma unroll
-    for (int pass = 0; pass < 3; pass++) {
-      if (4 * pass >= n) break;
-      const int k = 4 * pass + row;
-      uint32_t a = 0;
-      if (k < n) a = te_sad4(org, te_ipx4(nb, c, 8, order[k], i, j), 0);
-      a += (uint32_t)TE_DPP(a, 0xB1);
-      a += (uint32_t)TE_DPP(a, 0x4E);
-      a += (uint32_t)TE_DPP(a, 0x141);
-      a += (uint32_t)TE_DPP(a, 0x140);
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const int kk = 4 * pass + r;
-        const int sad = __builtin_amdgcn_readlane((int)a, 16 * r);
-        if (kk < n && sad < min_sad) {
-          best = order[kk];
-          min_sad = sad;
-        }
-      }
-    }
+    const int ch = TE_LANE & 15;
+    te_isearch8(nb, c, te_ld4(o + (ch >> 1) * F.osy + (ch & 1) * 4), order, n, min_sad, best);
   } else if (size == 16) {
     te_isearch<1>(nb, c, o, F.osy, size, order, n, min_sad, best);
   } else {  // 32, 64: few calls, many chunks per lane -- the prediction buffer keeps the code small
@@ -2492,6 +2521,169 @@ TE_NOINL int te_search_early_skip(const TeFrame &F_, TeSB &sb_, TeBlockInfo &bi_
   return early;
 }
 
+#if !defined(TE_HOST)
+// ---- the I-frame 8x8 leaf ----------------------------------------------------
+// An 8x8 CU of an I frame (64 of a superblock's 84 CU evaluations) without
+// tb-split or intra_rdo has one candidate and no smaller CU to lose to
+// (cost_small = 1 << 28 at the leaf), so whatever it codes is committed.  The
+// generic path still treats it as a candidate that may lose: a zeroed TeParam,
+// an encode into the candidate buffers, three SSD passes over them, the bits
+// read back and kept, two rewinds, the kept bits put back where they were, and
+// the reconstruction read back to be copied into the frame.  Here the CU is
+// coded once: the original pixels are loaded up front (luma one pixel per
+// lane, chroma on lanes 0..15), the search and the three register chains run
+// on them, each chain's SSD comes from the registers it holds, the syntax is
+// written once at the writer's position with the coefficient coder fed from the
+// level registers (ds_permute raster -> scan), and the reconstruction and the
+// cells go to the frame from registers.  Bits, costs, cells and reconstruction
+// equal the generic path's (te_mode_decision_intra + te_encode_final +
+// te_commit_block); F.leaf8 = 0 (THOR_ENC_LEAF8=0) keeps that path.
+// A call, not inlined into process_block: inlined, its live ranges on top of the three quadtree
+// levels' grew k_enc_rows' scratch frame (2 192 -> 2 672 B per lane).
+#ifdef TE_LEAF8_INLINE
+#define TE_LEAF8_FN TE_FN
+#else
+#define TE_LEAF8_FN TE_NOINL
+#endif
+__shared__ unsigned g_te_leaf8_n;  // CUs this worker coded here (k_enc_rows sums it into its profile)
+TE_LEAF8_FN uint32_t te_leaf8_intra(const TeFrame &F_, TeSB &sb_, TeBlockInfo &bi_) {
+  const TeFrame &F = *te_lds(&F_);
+  TeSB &sb = *te_lds(&sb_);
+  TeBlockInfo &bi = *te_lds(&bi_);
+  TE_P(TP_LEAF8);
+  const TeScratch S = te_here();
+  TeNbr &nbw = *S.nb;
+  const int ypos = bi.ypos, xpos = bi.xpos, yC = ypos / 2, xC = xpos / 2;
+  const int L = TE_LANE, hi = L >> 3, lo = L & 7, r = L & 15, ci = r >> 2, cj = r & 3;
+  const int qpY = F.qp + bi.delta_qp, qpC = te_chroma_qp(qpY);
+  const int ur = te_upright_avail(ypos, xpos, 8, F.W), dl = te_downleft_avail(ypos, xpos, 8, F.H);
+  if (L == 0) atomicAdd(&g_te_leaf8_n, 1u);
+  // the original pixels of the three components, and the search's view of the luma ones
+  const uint8_t *oYp = F.oy + ypos * F.osy + xpos;
+  const int oY = oYp[hi * F.osy + lo];
+  const uint32_t org4 = te_ld4(oYp + (r >> 1) * F.osy + (r & 1) * 4);
+  const int oU = F.ou[(yC + ci) * F.osc + xC + cj], oV = F.ov[(yC + ci) * F.osc + xC + cj];
+  int intra_mode = TE_DC, levY = 0, levU = 0, levV = 0, vY = 0, vU = 0, vV = 0, cy = 0, cu = 0, cv = 0;
+  uint32_t sy = 0, su = 0, sv = 0;
+  {  // luma: neighbours once, for the search and the chain
+    te_make_top_and_left(nbw, F.ry + ypos * F.rsy + xpos, F.rsy, nullptr, 0, 0, 0, ypos, xpos, 8, ur, dl, 0);
+    TeIpc c = te_ipx_setup(nbw, 8);
+    const TeNbr &nb = nbw;
+    {
+      TE_P(TP_LEAF8_SEARCH);
+      int min_sad = 1 << 30;
+      te_isearch8(nb, c, org4, te_intra_order, F.num_intra_modes == 4 ? 4 : 10, min_sad, intra_mode);
+    }
+    TE_P(TP_LEAF8_CHAINS);
+    int sl = 0, st = 0;  // DC of get_intra_prediction (position-aware), as te_enc_intra_c8
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      sl += nb.left[k];
+      st += nb.top[k];
+    }
+    c.dc = ((xpos != 0 ? sl : st) + (ypos != 0 ? st : sl) + 8) / 16;
+    cy = te_c8_core(te_ipx(nb, c, 8, intra_mode, hi, lo), oY, qpY, 2, levY, vY);
+    sy = te_sum((uint32_t)((oY - vY) * (oY - vY)));
+  }
+  const int rc = yC * F.rsc + xC;
+  {  // chroma: U, then V (4x4 chains on lanes 0..15)
+    TE_P(TP_LEAF8_CHAINS);
+#pragma clang loop unroll(disable)
+    for (int comp = 0; comp < 2; comp++) {  // (one copy of the chain's code)
+      te_make_top_and_left(nbw, (comp ? F.rv : F.ru) + rc, F.rsc, nullptr, 0, 0, 0, yC, xC, 4, ur, dl, 0);
+      TeIpc c = te_ipx_setup(nbw, 4);
+      const TeNbr &nb = nbw;
+      const int sl = nb.left[0] + nb.left[1] + nb.left[2] + nb.left[3], st = nb.top[0] + nb.top[1] + nb.top[2] + nb.top[3];
+      c.dc = ((xC != 0 ? sl : st) + (yC != 0 ? st : sl) + 4) / 8;
+      const int o = comp ? oV : oU;
+      int lev, v;
+      const int cb = te_c4_core(te_ipx(nb, c, 4, intra_mode, ci, cj), o, qpC, 3, lev, v);
+      const uint32_t s = te_sum(L < 16 ? (uint32_t)((o - v) * (o - v)) : 0u);
+      if (comp) levV = lev, vV = v, cv = cb, sv = s;
+      else levU = lev, vU = v, cu = cb, su = s;
+    }
+  }
+  // syntax, once, at the writer's position (write_block for an I-frame 8x8 CU: no super mode bit)
+  TeBits b = te_bits_local(sb.bits);
+  const int start = b.pos;
+  {
+    TE_P(TP_LEAF8_SYNTAX);
+    if (F.num_intra_modes <= 4) {
+      te_put(b, 2, intra_mode);
+    } else if (F.num_intra_modes <= 8) {
+      const int code = te_wb_map8[intra_mode];
+      te_put(b, te_wb_len8[code], te_wb_cw8[code]);
+    } else {
+      const int code = te_wb_map10[intra_mode];
+      te_put(b, te_wb_len10[code], te_wb_cw10[code]);
+    }
+    int code = te_wb_cbp[cy + (cu << 1) + (cv << 2)];
+    if (bi.ctx.cbp == 0 && code < 2) code = 1 - code;
+    te_put_vlc(b, 0, code);
+    // each coded component's levels from raster to scan order: lane r sends its level to lane zz(r)
+    const int toY = te_zz(8, L) * 4, toC = (L < 16 ? (int)((0xfea9db83c7426510ull >> (4 * r)) & 15) : L) * 4;
+#pragma clang loop unroll(disable)
+    for (int s = 0; s < 3; s++) {  // one call site of the coefficient coder
+      if (!(s == 0 ? cy : (s == 1 ? cu : cv))) continue;
+      const int lev = s == 0 ? levY : (s == 1 ? levU : levV);
+      const int sc = __builtin_amdgcn_ds_permute(s == 0 ? toY : toC, lev);
+      TeScanRegs R;
+      R.v0 = (s == 0 || L < 16) ? sc : 0;
+      R.v1 = R.v2 = R.v3 = 0;
+      R.nz[0] = __ballot(R.v0 != 0);
+      R.nz[1] = R.nz[2] = R.nz[3] = 0;
+      b = te_write_coeff_scan(b, R, s == 0 ? 8 : 4, 2 | (s != 0));
+    }
+  }
+  const int nbits = b.pos - start;
+  sb.bits = b;
+  TE_TR(F.frame_num, 2, ypos, xpos, 8 | TE_INTRA << 8 | 1 << 12, intra_mode << 12, nbits, cy | cu << 1 | cv << 2);
+  // cost_calc (te_cost's formula)
+  const double prod = F.lambda * (double)nbits;
+  uint32_t cost = sy + su + sv + (uint32_t)(int32_t)(prod + 0.5);
+  if (cost > (1u << 30)) cost = 1u << 30;
+  TE_TR(F.frame_num, 3, ypos, xpos, 8, sy, su + sv, cost);
+  TE_TR(F.frame_num, 5, ypos, xpos, 8, cost, TE_INTRA, TE_MAX_UINT32);
+  {  // commit: reconstruction, levels, cells and the block's parameters from registers
+    TE_P(TP_LEAF8_COMMIT);
+    F.ry[(ypos + hi) * F.rsy + xpos + lo] = (uint8_t)vY;
+    int16_t *cf = bi.bp.coeff;
+    cf[L] = (int16_t)levY;
+    if (L < 16) {
+      F.ru[rc + ci * F.rsc + cj] = (uint8_t)vU;
+      F.rv[rc + ci * F.rsc + cj] = (uint8_t)vV;
+      cf[64 + L] = (int16_t)levU;
+      cf[128 + L] = (int16_t)levV;
+    }
+    if (L < 4) {
+      TeCell c;
+      c.ip.mv0.x = c.ip.mv0.y = c.ip.mv1.x = c.ip.mv1.y = 0;
+      c.ip.ref_idx0 = c.ip.ref_idx1 = 0;
+      c.ip.bipred_flag = -1;
+      c.mode = TE_INTRA;
+      c.size = 8;
+      c.tb_split = 0;
+      c.pb_part = 0;
+      c.cbp_y = (uint8_t)cy;
+      c.cbp_u = (uint8_t)cu;
+      c.cbp_v = (uint8_t)cv;
+      c.rsv = 0;
+      F.cells[(ypos / 4 + (L >> 1)) * (F.W / 4) + xpos / 4 + (L & 1)] = c;
+    }
+    TeParam &p = bi.bp;  // (zeroed with bi: vectors, reference indices, skip_idx, pb_part, tb_param, tb_split)
+    p.mode = TE_INTRA;
+    p.intra_mode = intra_mode;
+    p.dir = -1;
+    p.cbp_y = cy;
+    p.cbp_u = cu;
+    p.cbp_v = cv;
+    bi.final_encode = 1;
+    te_sync();
+  }
+  return cost;
+}
+#endif
+
 // ---- process_block, enc/encode_block.c:2787-3033 ----------------------------
 // Template over the CU size: the quadtree recursion unrolls at compile time
 // (64 -> 32 -> 16 -> 8); level L = log2(64 / SIZE) owns TeScratch::lv[L].
@@ -2558,6 +2750,14 @@ TE_FN uint32_t te_process_block_b(const TeFrame &F_, TeSB &sb_, int ypos, int xp
     bi.num_skip = te_mv_skip(ypos, xpos, W, H, SIZE, F.cells, bi.skip_c);
     bi.num_merge = te_mv_skip(ypos, xpos, W, H, SIZE, F.cells, bi.merge_c);
   }
+#if !defined(TE_HOST)
+  if constexpr (SIZE == 8 && TE_C4) {  // the leaf CU of an I frame: coded once, in registers (te_leaf8_intra)
+    if (te_uni(F.leaf8 && ft == TE_I && encode_this && !F.enable_tb_split && !F.intra_rdo)) {  // (wave-uniform)
+      const uint32_t leaf_cost = te_leaf8_intra(F, sb, bi);  // (TE_MIN is a macro: one evaluation)
+      return TE_MIN(leaf_cost, cost_small);
+    }
+  }
+#endif
   if (encode_this && ft != TE_I && F.early_skip_thr > 0.0f) {
     bi.final_encode = 2;
     uint32_t es_cost = 0;

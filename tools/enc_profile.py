@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "thor_amd", "libthor_amd_prof.so")
 CATS = ["wcoef", "wblock", "inter_comp", "intra_comp", "enc_block", "cost", "search_intra", "me", "mode",
         "es_check", "es_search", "commit", "mc_y", "mc_c", "fwd", "quant", "inv", "ipred", "topleft", "sad", "sb",
-        "wait"]
+        "wait", "leaf8", "leaf8_search", "leaf8_chains", "leaf8_syntax", "leaf8_commit"]
 
 
 def build():
