@@ -270,7 +270,8 @@ int thor_dec_set_stream(thor_dec_t *d, void *stream);
  * encode_and_reconstruct_block_inter / _intra's per-TU body
  * (enc/encode_block.c:1434-1518): get_residual (:484-493) -> transform
  * (common/transform.c:249-330) -> quantize (enc/encode_block.c:75-172,
- * rdoq 0) -> [cbp] dequantize + inverse_transform (common/common_block.c:
+ * always rdoq 0: the descriptor has no field for it; full RDOQ is in the
+ * device encoder and the L2 quantize) -> [cbp] dequantize + inverse_transform (common/common_block.c:
  * 132-146, common/transform.c:432-518) -> reconstruct_block
  * (common/common_block.c:148-156) or rec = pred -> SSD(orig, rec).
  * 32 bytes, naturally aligned. */
@@ -355,7 +356,7 @@ typedef struct thor_enc_params {
 void thor_enc_default_params(thor_enc_params_t *p);
 /* 0 if the parameters are supported by the device encoder, else THOR_ERR_ARG
  * (check_parameters, enc/strings.c:431-479, plus this build's limits:
- * rdoq 0, sync 0). */
+ * rdoq 0 or 1, sync 0). */
 int thor_enc_check_params(const thor_enc_params_t *p);
 
 /* A device-resident encoder context: the reference's frame loop

@@ -9,16 +9,16 @@
  *   make_top_and_left         common/intra_prediction.h:31-32
  *   dequantize                common/common_block.h:38
  *   reconstruct_block         common/common_block.h:39
- *   quantize                  enc/encode_block.c:75 (rdoq = 0)
+ *   quantize                  enc/encode_block.c:75 (rdoq 0 or 1)
  *
  * Each runs on the GPU: the call's inputs are staged to device memory, one
  * launch (two per deblocking direction) computes, the result is copied back.
  * The frame-level deblocking is the batched decoder's own kernels over the
  * caller's deblock_data; the block-level calls are launch-latency bound and
  * exist for drop-in completeness (the batched API, thor_amd.h, is the fast
- * path).  Like the reference these return no status; a GPU failure, or a
- * request this build does not implement (quantize with rdoq = 1), aborts with
- * a message instead of returning wrong data.
+ * path).  Like the reference these return no status; a GPU failure, or an
+ * argument out of range, aborts with a message instead of returning wrong
+ * data.
  */
 #ifndef THOR_L2_H
 #define THOR_L2_H
@@ -70,7 +70,8 @@ void dequantize(int16_t *coeff, int16_t *rcoeff, int quant, int size);
 /* common/common_block.h:39 */
 void reconstruct_block(int16_t *block, uint8_t *pblock, uint8_t *rec, int size, int stride);
 /* enc/encode_block.c:75 -- writes the top-left min(size,16)^2 of coeffq
- * (size x size layout), returns cbp; rdoq must be 0 */
+ * (size x size layout), returns cbp; rdoq 1: full RDOQ
+ * (:179-472), one wave walking the coded events */
 int quantize(int16_t *coeff, int16_t *coeffq, int qp, int size, int coeff_block_type, int rdoq);
 
 #ifdef __cplusplus

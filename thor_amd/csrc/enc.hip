@@ -1089,7 +1089,7 @@ static int enc_prepare(thor_enc *e, const uint8_t *orig, int orig_stride, TeJob 
   F.sync = P.sync;
   F.early_skip_thr = P.early_skip_thr;
   F.es_thr = e->es_thr;
-  F.leaf8 = enc_leaf8_on();
+  F.leaf8 = enc_leaf8_on() && !P.rdoq;  // (te_leaf8_intra is an rdoq-0 quantiser: full RDOQ keeps the generic path)
   J.sb_words = e->sb_words;
   J.sb_nbits = e->sb_nbits;
   J.deps = e->deps;

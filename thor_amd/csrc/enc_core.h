@@ -20,6 +20,8 @@
 #include <string.h>
 
 #include <stdlib.h>
+
+#include "enc_lambda.h"
 #if defined(TE_HOST)
 #define TE_FN static inline
 #define TE_NOINL static
@@ -320,7 +322,7 @@ struct TeFrame {
   int speed, enable_tb_split, enable_pb_split, enable_bipred, max_delta_qp, delta_qp_step;
   int intra_rdo, use_block_contexts, rdoq, sync;
   float early_skip_thr;
-  int leaf8;          // device: I-frame 8x8 CUs take te_leaf8_intra (THOR_ENC_LEAF8, default on); fills the padding
+  int leaf8;          // device: I-frame 8x8 CUs take te_leaf8_intra (THOR_ENC_LEAF8, default on; 0 under rdoq); fills the padding
   const int *es_thr;  // early-skip thresholds [2][52][4], te_es_thresholds (host)
 };
 

@@ -14,13 +14,7 @@
 
 #define TE_GOP_MAX_REF 8
 
-// squared_lambda_QP, enc/encode_frame.c:37-44
-static const double te_sq_lambda[52] = {
-    0.0382,    0.0485,    0.0615,    0.0781,    0.0990,    0.1257,    0.1595,    0.2023,    0.2567,    0.3257,    0.4132,
-    0.5243,    0.6652,    0.8440,    1.0709,    1.3588,    1.7240,    2.1874,    2.7754,    3.5214,    4.4679,    5.6688,
-    7.1926,    9.1259,    11.5789,   14.6912,   18.6402,   23.6505,   30.0076,   38.0735,   48.3075,   61.2922,   77.7672,
-    98.6706,   125.1926,  158.8437,  201.5399,  255.7126,  324.4467,  411.6560,  522.3067,  662.6996,  840.8294,  1066.8393,
-    1353.5994, 1717.4389, 2179.0763, 2764.7991, 3507.9607, 4450.8797, 5647.2498, 7165.1970};
+#include "enc_lambda.h"  // te_sq_lambda: squared_lambda_QP, enc/encode_frame.c:37-44
 
 static inline int te_log2i_host(unsigned x) {
   int r = 0;
@@ -217,7 +211,7 @@ struct TeGop {
       const float c[5] = {P.lambda_coeffB0, P.lambda_coeffB1, P.lambda_coeffB2, P.lambda_coeffB3, P.lambda_coeffB};
       lc = c[f.b_level < 4 ? f.b_level : 4];
     }
-    f.lambda = lc * te_sq_lambda[f.qp];
+    f.lambda = lc * te_sq_lambda(f.qp);
   }
 
   // after a frame is coded: slide the window (enc/encode_frame.c:165-177) and
@@ -394,7 +388,9 @@ static inline int te_check_params(const thor_enc_params_t *p) {
   if (p->num_reorder_pics < 0 || nrp1 > 16 || p->max_delta_qp < 0) return THOR_ERR_ARG;
   if (p->max_delta_qp > 0 && p->delta_qp_step < 1) return THOR_ERR_ARG;
   if (p->skip < 0) return THOR_ERR_ARG;
-  if (p->rdoq) return THOR_ERR_ARG;  // full RDOQ is not implemented
-  if (p->sync) return THOR_ERR_ARG;  // WPP row sync (requires encoder_speed 2 in the reference) is not implemented
+  if (p->rdoq != 0 && p->rdoq != 1) return THOR_ERR_ARG;  // 1: full RDOQ (te_rdoq, enc_pix.h)
+  // -sync 1: its motion search reads candidates left by the previous superblock in raster
+  // order (enc/encode_block.c:1082-1095), which rows coded in parallel cannot reproduce
+  if (p->sync) return THOR_ERR_ARG;
   return THOR_OK;
 }

@@ -797,11 +797,193 @@ TE_FN void te_fwd_tx(TeTx &X, int size, int fast) {
   else te_fwd_gen<32>(X, in, sh1, sh2);
 }
 
-// quantize, enc/encode_block.c:75-172 (rdoq = 0): X.C -> levels (q x q
+// Full RDOQ, the rdoq = 1 tail of quantize (enc/encode_block.c:179-472), on a
+// block with cbp != 0: X.S (levels, scan order) and X.O (coefficients, scan
+// order) as te_quant_t leaves them after RDOQ light.  Picks the end-of-block
+// position of least distortion + lambda * rate, clears the levels behind it
+// in X.S and returns the new cbp.  No level changes value, but for the chroma
+// "single DC" candidate, which writes 0 / 1 for a positive / negative DC
+// coefficient (:446-457 -- never -1).
+//
+// The reference walks positions 0..last_pos with write_coeff's state machine,
+// cost0 += err + (int)(lambda * bit + 0.5), and at every coded event (a
+// non-zero level, or the zero that ends a level mode) tries
+//   cost1 = cost0 + sum_{p > pos} coeff[p]^2 + (int)(lambda * eob_bits + 0.5)
+// in wrapping uint32, first minimum wins.  A zero level reconstructs to zero,
+// so with d[p] = err[p] - coeff[p]^2 (0 at zero levels), D its inclusive scan
+// and T the sum of coeff^2 over all N positions,
+//   cost1 = T + D[pos] + (rate terms of the events up to pos) + eob term:
+// d, D and T are lane-parallel (position lane + 64 k in lane's k-th
+// register, one DPP row scan plus three readlanes per 64 positions); the walk
+// itself is uniform and steps from event to event, runs of zeros skipped with
+// ctz on the non-zero ballots, levels and D read back with readlane.  Rate
+// terms are (int)(double * double + 0.5), no contraction, as the reference.
+TE_FN uint32_t te_rdoq_rate(double lambda, int bit) { return (uint32_t)(int)(lambda * (double)bit + 0.5); }
+// bits of an EOB sent after position pos, whose level is `level` (:228-263); eob_code: those of the EOB event itself
+TE_FN int te_rdoq_eob(int pos, int level, int N, int chroma, int eob_code) {
+  if (pos >= N - 1) return 0;
+  if (level > 1) return te_quote_vlc((level > 3 && chroma == 0) ? 1 : 0, 0) + (pos < N - 2 ? eob_code : 0);
+  return eob_code;
+}
+TE_FN void te_rdoq_try(uint32_t cost1, int pos, uint32_t &min_cost, int &min_pos) {
+  if (cost1 < min_cost) {  // (strict: the earliest minimum wins)
+    min_cost = cost1;
+    min_pos = pos;
+  }
+}
+// first set bit at or behind p (p < 256) of the 256-bit mask m0..m3, or 256
+TE_FN int te_rdoq_next(uint64_t nz0, uint64_t nz1, uint64_t nz2, uint64_t nz3, int p) {
+  const uint64_t from = ~0ULL << (p & 63);
+  const uint64_t m0 = p < 64 ? nz0 & from : 0, m1 = p < 64 ? nz1 : (p < 128 ? nz1 & from : 0),
+                 m2 = p < 128 ? nz2 : (p < 192 ? nz2 & from : 0), m3 = p < 192 ? nz3 : nz3 & from;
+  if (m0) return __builtin_ctzll(m0);
+  if (m1) return 64 + __builtin_ctzll(m1);
+  if (m2) return 128 + __builtin_ctzll(m2);
+  return m3 ? 192 + __builtin_ctzll(m3) : 256;
+}
+#if !defined(TE_HOST)
+// scan positions 64 k + lane: the level (sv), the inclusive scan of d over positions 0..pos (dv; carry: the total
+// of the registers before), coeff^2 added to o2, the non-zero ballot
+TE_FN void te_rdoq_chunk(const TeTx &X, int k, int N, int dscale, int lshift, int add, int rshift, uint32_t &carry,
+                         uint32_t &o2, int &sv, uint32_t &dv, uint64_t &nz) {
+  const int l = TE_LANE, pos = l + 64 * k;
+  int s = 0, o = 0;
+  if (pos < N) {
+    s = X.S[pos];
+    o = X.O[pos];
+  }
+  const int e = (((s * dscale) * (1 << lshift) + add) >> rshift) - o;
+  uint32_t v = (uint32_t)e * (uint32_t)e - (uint32_t)(o * o);
+  o2 += (uint32_t)(o * o);
+  // inclusive scan within each row of 16 lanes (row_shr 1, 2, 4, 8; lanes shifted in from outside read 0) ...
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);
+  // ... then the totals of the rows below, and of the positions before this register
+  const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)v, 15), r1 = (uint32_t)__builtin_amdgcn_readlane((int)v, 31),
+                 r2 = (uint32_t)__builtin_amdgcn_readlane((int)v, 47), r3 = (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+  v += carry + (l >= 16 ? r0 : 0u) + (l >= 32 ? r1 : 0u) + (l >= 48 ? r2 : 0u);
+  carry += r0 + r1 + r2 + r3;
+  sv = s;
+  dv = v;
+  nz = __ballot(s != 0);
+}
+#endif
+TE_NOINL int te_rdoq(TeTx &X_, int qp, int size, int type, int last_pos) {
+  TeTx &X = *te_lds(&X_);
+  qp = te_uni(qp);
+  size = te_uni(size);
+  type = te_uni(type);
+  last_pos = te_uni(last_pos);
+  const int chroma = type & 1;
+  const int lg = te_log2(size), q = TE_MIN(size, 16), N = q * q;
+  const int lshift = qp / 6, rshift = lg - 1, dscale = te_gdequant[qp % 6], add = 1 << (rshift - 1);  // :187-190
+  const double lambda = 1.0 * te_sq_lambda(qp) * (double)(1 << 2 * (7 - lg));                        // :195
+  uint32_t T = 0;
+  uint64_t nz0 = 0, nz1 = 0, nz2 = 0, nz3 = 0;  // non-zero levels, scan order
+#if defined(TE_HOST)
+  uint32_t D[256];
+  {
+    uint32_t acc = 0;
+    for (int pos = 0; pos < 256; pos++) {
+      const int s = pos < N ? X.S[pos] : 0, o = pos < N ? X.O[pos] : 0;
+      const int e = (((s * dscale) * (1 << lshift) + add) >> rshift) - o;
+      if (s) (pos < 64 ? nz0 : (pos < 128 ? nz1 : (pos < 192 ? nz2 : nz3))) |= 1ULL << (pos & 63);
+      acc += (uint32_t)e * (uint32_t)e - (uint32_t)(o * o);
+      D[pos] = acc;
+      T += (uint32_t)(o * o);
+    }
+  }
+#define TE_RDOQ_S(p) ((int)X.S[p])
+#define TE_RDOQ_D(p) D[p]
+#else
+  // (plain scalars, every index a constant: all of it stays in registers)
+  int s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+  uint32_t d0 = 0, d1 = 0, d2 = 0, d3 = 0;
+  {
+    uint32_t carry = 0, o2 = 0;
+    te_rdoq_chunk(X, 0, N, dscale, lshift, add, rshift, carry, o2, s0, d0, nz0);
+    te_rdoq_chunk(X, 1, N, dscale, lshift, add, rshift, carry, o2, s1, d1, nz1);
+    te_rdoq_chunk(X, 2, N, dscale, lshift, add, rshift, carry, o2, s2, d2, nz2);
+    te_rdoq_chunk(X, 3, N, dscale, lshift, add, rshift, carry, o2, s3, d3, nz3);
+    T = te_sum(o2);
+  }
+#define TE_RDOQ_S(p) __builtin_amdgcn_readlane((p) < 64 ? s0 : ((p) < 128 ? s1 : ((p) < 192 ? s2 : s3)), (p) & 63)
+#define TE_RDOQ_D(p) \
+  ((uint32_t)__builtin_amdgcn_readlane((int)((p) < 64 ? d0 : ((p) < 128 ? d1 : ((p) < 192 ? d2 : d3))), (p) & 63))
+#endif
+  // the code of the EOB event is a constant of the block
+  const int cn_eob = te_find_code(0, 0, 0, chroma, 1);
+  const int eob_code = (chroma && size <= 8) ? te_quote_vlc(0, cn_eob) : (cn_eob == 0 ? 2 : te_quote_vlc(2, cn_eob + 1));
+  uint32_t rate = 0, min_cost = 0xffffffffu;  // rate: cost0's rate terms; cost0 = T - (suffix sum) + D + rate
+  int min_pos = 0;
+  int pos = 0, level = 1, level_mode = 1;
+  while (pos <= last_pos) {  // :202-371
+    if (level_mode) {
+      int vlc_adaptive = (level > 3 && chroma == 0) ? 1 : 0;
+      while (pos <= last_pos && level > 0) {
+        level = te_abs(TE_RDOQ_S(pos));
+        int bit = te_quote_vlc(vlc_adaptive, level) + (level > 0);
+        if (chroma == 0) vlc_adaptive = level > 3;
+        if (chroma == 1 && pos == 0 && level == 1) bit = 1;  // (cost0 only, :220-221)
+        rate += te_rdoq_rate(lambda, bit);
+        te_rdoq_try(T + TE_RDOQ_D(pos) + rate + te_rdoq_rate(lambda, te_rdoq_eob(pos, level, N, chroma, eob_code)), pos,
+                    min_cost, min_pos);
+        pos++;
+      }
+    }
+    if (pos > last_pos) break;
+    // run mode: zeros add their coeff^2 only (in D); the next event is the next non-zero level
+    const int start = pos, maxrun = N - pos - 1;
+    pos = te_rdoq_next(nz0, nz1, nz2, nz3, pos);
+    if (pos > last_pos) break;  // (levels are zero behind last_pos)
+    const int c = TE_RDOQ_S(pos);
+    level = te_abs(c);
+    const int cn = te_find_code(pos - start, level, maxrun, chroma, 0);
+    int bit = (chroma && size <= 8) ? te_quote_vlc(10, cn) : (cn == 0 ? 2 : te_quote_vlc(2, cn + 1));
+    bit += level > 1 ? te_quote_vlc(0, 2 * (level - 2) + (c < 0 ? 1 : 0)) : 1;
+    rate += te_rdoq_rate(lambda, bit);
+    te_rdoq_try(T + TE_RDOQ_D(pos) + rate + te_rdoq_rate(lambda, te_rdoq_eob(pos, level, N, chroma, eob_code)), pos,
+                min_cost, min_pos);
+    pos++;
+    level_mode = level > 1;
+  }
+  if (T < min_cost) {  // cbp = 0, :432-441
+    min_pos = -1;
+    min_cost = T;
+  }
+  int dc = 0, dc_sign = 0;
+  if (chroma) {  // a single DC level of 0 / 1, :443-459 (min_cost stays)
+    const int o = X.O[0];
+    dc_sign = o < 0 ? 1 : 0;
+    const int e = o - (((dc_sign * dscale) * (1 << lshift) + add) >> rshift);
+    const uint32_t cost1 = (uint32_t)e * (uint32_t)e + te_rdoq_rate(lambda, 1) + (T - (uint32_t)(o * o));
+    if (cost1 < min_cost) {
+      min_pos = 0;
+      dc = 1;
+    }
+  }
+#undef TE_RDOQ_S
+#undef TE_RDOQ_D
+  int any = 0;  // :461-471 (each lane rewrites the positions it read above)
+  for (int p = TE_LANE; p < N; p += TE_NL) {
+    int s = X.S[p];
+    if (p > min_pos) X.S[p] = (int16_t)(s = 0);
+    else if (dc && p == 0) X.S[p] = (int16_t)(s = dc_sign);
+    any |= s != 0;
+  }
+  const int cbp = te_any(any);
+  te_sync();
+  return cbp;
+}
+
+// quantize, enc/encode_block.c:75-172, and with `rdoq` (a constant in the
+// encoder's chains) its full-RDOQ tail (:179-472, te_rdoq): X.C -> levels (q x q
 // raster) in X.C.  Returns cbp.  With `coef`: the levels go there (raster)
 // and X.C holds them dequantized instead -- the chains' quantize, level copy
 // and dequantize in one pass (X.C is only read when cbp != 0).
-TE_FN int te_quant_t(TeTx &X, int qp, int size, int type, int16_t *coef) {
+TE_FN int te_quant_t(TeTx &X, int qp, int size, int type, int16_t *coef, int rdoq) {
   TE_P(TP_QUANT);
   const int intra = (type >> 1) & 1, chroma = type & 1;
   const int lg = te_log2(size), q = TE_MIN(size, 16), nq = q * q;
@@ -838,7 +1020,7 @@ TE_FN int te_quant_t(TeTx &X, int qp, int size, int type, int16_t *coef) {
     X.S[pos] = (int16_t)lev;
     X.O[pos] = (int16_t)cv[t];
   }
-  const int cbp = te_any(any);
+  int cbp = te_any(any);
   te_sync();
   if (cbp) {  // "RDOQ light" (:134-168), serial over the scan.  Only positions whose
     // initial level exceeds 1 can trigger: earlier iterations modify indices
@@ -902,6 +1084,7 @@ TE_FN int te_quant_t(TeTx &X, int qp, int size, int type, int16_t *coef) {
 #undef TE_NZ
   }
   te_sync();
+  if (rdoq && cbp) cbp = te_rdoq(X, qp, size, type, last_pos);
   if (coef) {  // the levels to the candidate's coefficient tile, X.C dequantized (common_block.c:132-146)
     const int rshift = lg - 1, add = 1 << (rshift - 1), lshift = qp / 6, dscale = te_gdequant[qp % 6];
 #pragma unroll
@@ -923,7 +1106,7 @@ TE_FN int te_quant_t(TeTx &X, int qp, int size, int type, int16_t *coef) {
   te_sync();
   return cbp;
 }
-TE_FN int te_quant(TeTx &X, int qp, int size, int type) { return te_quant_t(X, qp, size, type, nullptr); }
+TE_FN int te_quant(TeTx &X, int qp, int size, int type, int rdoq) { return te_quant_t(X, qp, size, type, nullptr, rdoq); }
 
 // dequantize (common/common_block.c:132-146), int16 truncating store, in place
 TE_FN void te_dequant(TeTx &X, int qp, int size) {
@@ -937,11 +1120,11 @@ TE_FN void te_dequant(TeTx &X, int qp, int size) {
 #define TE_QUANT_FUSE 1
 #endif
 // quantize -> the levels into the candidate's tile -> X.C dequantized (when cbp)
-TE_FN int te_quant_chain(TeTx &X, int qp, int size, int type, int16_t *coef) {
+TE_FN int te_quant_chain(TeTx &X, int qp, int size, int type, int16_t *coef, int rdoq) {
 #if TE_QUANT_FUSE
-  return te_quant_t(X, qp, size, type, coef);
+  return te_quant_t(X, qp, size, type, coef, rdoq);
 #else
-  const int cbp = te_quant(X, qp, size, type);
+  const int cbp = te_quant(X, qp, size, type, rdoq);
   const int q = TE_MIN(size, 16);
   for (int e = TE_LANE; e < q * q; e += TE_NL) coef[e] = (int16_t)X.C[e];
   if (cbp) te_dequant(X, qp, size);

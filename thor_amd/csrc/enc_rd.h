@@ -293,8 +293,13 @@ TE_FN void te_recon(uint8_t *rec, int rs, const uint8_t *pb, int ps, const TeTx 
 // encode_and_reconstruct_block_inter, enc/encode_block.c:1469-1532, one
 // component: orig (frame, stride os) - pred -> levels (tiles of `coef`) ->
 // rec (compact, stride size).  Returns cbp (4-bit mask when tb-split).
-TE_NOINL int te_enc_inter_comp(const TeFrame &F_, const uint8_t *org, int os, int size, int qp,
-                               const uint8_t *pb_, int16_t *coef, uint8_t *rec, int type, int tb_split, int ts) {
+// RQ: quantize with full RDOQ (-rdoq 1, te_rdoq).  Its call lives in copies of
+// the chains of their own (te_enc_inter_comp_rq, te_enc_intra_comp_rq), chosen
+// by F.rdoq in te_encode_block_t: the rdoq-0 chains stay free of calls, hence
+// of the register saves a call would put into their prologues.
+template <bool RQ>
+TE_FN int te_enc_inter_comp_t(const TeFrame &F_, const uint8_t *org, int os, int size, int qp,
+                              const uint8_t *pb_, int16_t *coef, uint8_t *rec, int type, int tb_split, int ts) {
   const TeFrame &F = *te_lds(&F_);
   const TeScratch S = te_here();
   const uint8_t *pb = te_lds(pb_);
@@ -309,7 +314,7 @@ TE_NOINL int te_enc_inter_comp(const TeFrame &F_, const uint8_t *org, int os, in
       const int i = (t >> 1) * s2, j = (t & 1) * s2;
       te_residual_tx(X, org + i * os + j, os, pb + i * size + j, size, s2, fast);
       te_fwd_tx(X, s2, fast);
-      const int bit = te_quant_chain(X, qp, s2, type, coef + t * ts);
+      const int bit = te_quant_chain(X, qp, s2, type, coef + t * ts, RQ);
       if (bit) te_inv_tx(X, s2);
       te_recon(rec + i * size + j, size, pb + i * size + j, size, X, s2, bit);
       cbp = (cbp << 1) + bit;
@@ -319,10 +324,18 @@ TE_NOINL int te_enc_inter_comp(const TeFrame &F_, const uint8_t *org, int os, in
   const int fast = (size == 64 && F.speed > 0) || F.speed > 1;
   te_residual_tx(X, org, os, pb, size, size, fast);
   te_fwd_tx(X, size, fast);
-  cbp = te_quant_chain(X, qp, size, type, coef);
+  cbp = te_quant_chain(X, qp, size, type, coef, RQ);
   if (cbp) te_inv_tx(X, size);
   te_recon(rec, size, pb, size, X, size, cbp);
   return cbp;
+}
+TE_NOINL int te_enc_inter_comp(const TeFrame &F, const uint8_t *org, int os, int size, int qp, const uint8_t *pb,
+                               int16_t *coef, uint8_t *rec, int type, int tb_split, int ts) {
+  return te_enc_inter_comp_t<false>(F, org, os, size, qp, pb, coef, rec, type, tb_split, ts);
+}
+TE_NOINL int te_enc_inter_comp_rq(const TeFrame &F, const uint8_t *org, int os, int size, int qp, const uint8_t *pb,
+                                  int16_t *coef, uint8_t *rec, int type, int tb_split, int ts) {
+  return te_enc_inter_comp_t<true>(F, org, os, size, qp, pb, coef, rec, type, tb_split, ts);
 }
 
 #if !defined(TE_HOST)
@@ -434,9 +447,10 @@ TE_FN TeIpc te_ipx_setup(TeNbr &nb, int n) {
 #endif
 // encode_and_reconstruct_block_intra, enc/encode_block.c:1398-1467, one
 // component.  rf / fs: the frame being reconstructed at the CU origin.
-TE_FN int te_enc_intra_comp(const TeFrame &F_, const uint8_t *org, int os, const uint8_t *rf, int fs,
-                               int ypos, int xpos, int size, int qp, uint8_t *pb_, int16_t *coef, uint8_t *rec, int type,
-                               int tb_split, int mode, int ur, int dl, int ts) {
+template <bool RQ>
+TE_FN int te_enc_intra_comp_t(const TeFrame &F_, const uint8_t *org, int os, const uint8_t *rf, int fs,
+                              int ypos, int xpos, int size, int qp, uint8_t *pb_, int16_t *coef, uint8_t *rec, int type,
+                              int tb_split, int mode, int ur, int dl, int ts) {
   const TeFrame &F = *te_lds(&F_);
   const TeScratch S = te_here();
   uint8_t *pb = te_lds(pb_);
@@ -452,7 +466,7 @@ TE_FN int te_enc_intra_comp(const TeFrame &F_, const uint8_t *org, int os, const
       te_intra_pred(*S.nb, ypos + i, xpos + j, s2, pb, mode, 0);
       te_residual_tx(X, org + i * os + j, os, pb, s2, s2, fast);
       te_fwd_tx(X, s2, fast);
-      const int bit = te_quant_chain(X, qp, s2, type, coef + t * ts);
+      const int bit = te_quant_chain(X, qp, s2, type, coef + t * ts, RQ);
       if (bit) te_inv_tx(X, s2);
       te_recon(rec + i * size + j, size, pb, s2, X, s2, bit);
       cbp = (cbp << 1) + bit;
@@ -463,10 +477,16 @@ TE_FN int te_enc_intra_comp(const TeFrame &F_, const uint8_t *org, int os, const
   te_intra_pred(*S.nb, ypos, xpos, size, pb, mode, 0);
   te_residual_tx(X, org, os, pb, size, size, fast);
   te_fwd_tx(X, size, fast);
-  const int cbp = te_quant_chain(X, qp, size, type, coef);
+  const int cbp = te_quant_chain(X, qp, size, type, coef, RQ);
   if (cbp) te_inv_tx(X, size);
   te_recon(rec, size, pb, size, X, size, cbp);
   return cbp;
+}
+TE_FN int te_enc_intra_comp(const TeFrame &F, const uint8_t *org, int os, const uint8_t *rf, int fs, int ypos, int xpos,
+                            int size, int qp, uint8_t *pb, int16_t *coef, uint8_t *rec, int type, int tb_split,
+                            int mode, int ur, int dl, int ts) {
+  return te_enc_intra_comp_t<false>(F, org, os, rf, fs, ypos, xpos, size, qp, pb, coef, rec, type, tb_split, mode, ur,
+                                    dl, ts);
 }
 
 #if !defined(TE_HOST)
@@ -839,6 +859,13 @@ TE_NOINL int te_enc_intra_comp_nc(const TeFrame &F_, const uint8_t *org, int os,
                                   int tb_split, int mode, int ur, int dl, int ts) {
   return te_enc_intra_comp(F_, org, os, rf, fs, ypos, xpos, size, qp, pb_, coef, rec, type, tb_split, mode, ur, dl, ts);
 }
+// ... and one with full RDOQ, for every frame type
+TE_NOINL int te_enc_intra_comp_rq(const TeFrame &F, const uint8_t *org, int os, const uint8_t *rf, int fs, int ypos,
+                                  int xpos, int size, int qp, uint8_t *pb, int16_t *coef, uint8_t *rec, int type,
+                                  int tb_split, int mode, int ur, int dl, int ts) {
+  return te_enc_intra_comp_t<true>(F, org, os, rf, fs, ypos, xpos, size, qp, pb, coef, rec, type, tb_split, mode, ur,
+                                   dl, ts);
+}
 // IFR: the I-frame copy, with the intra chains inlined (no call per
 // component); P / B frames use the other, whose body stays small for the
 // inter candidates that dominate them.
@@ -859,21 +886,23 @@ TE_FN int te_encode_block_t(const TeFrame &F_, TeBits &b_, TeBlockInfo &bi_, TeP
   const uint8_t *oY = F.oy + ypos * F.osy + xpos, *oU = F.ou + yC * F.osc + xC, *oV = F.ov + yC * F.osc + xC;
   int cy = 0, cu = 0, cv = 0;
   const int itype = (F.frame_type == TE_I) << 1;  // quantisation type follows the frame type (:1764)
+  // full RDOQ: the generic chains' copies that call te_rdoq (the register-resident 8x8 / 4x4 chains are rdoq-0 quantisers)
+  const int rq = F.rdoq;
   if (mode == TE_INTRA) {
     const int ur = te_upright_avail(ypos, xpos, size, F.W), dl = te_downleft_avail(ypos, xpos, size, F.H);
-#define TE_INTRA_CHAINS(fn)                                                                                        \
-  if (TE_C4 && size == 8 && !tb_split)                                                                             \
+#define TE_INTRA_CHAINS(fn, C4)                                                                                    \
+  if (C4 && size == 8 && !tb_split)                                                                                \
     cy = te_enc_intra_c8(oY, F.osy, F.ry + ypos * F.rsy + xpos, F.rsy, ypos, xpos, qpY, p.coeff, recY, itype | 0,   \
                          p.intra_mode, ur, dl, te_nb_key(ypos, xpos, 8));                                          \
   else                                                                                                             \
     cy = fn(F, oY, F.osy, F.ry + ypos * F.rsy + xpos, F.rsy, ypos, xpos, size, qpY, S.pb, p.coeff, recY, itype | 0,  \
             tb_split, p.intra_mode, ur, dl, p.ts);                                                                 \
-  if (TE_C4 && sC == 8 && !(tb_split && size > 8)) {                                                              \
+  if (C4 && sC == 8 && !(tb_split && size > 8)) {                                                                 \
     cu = te_enc_intra_c8(oU, F.osc, F.ru + yC * F.rsc + xC, F.rsc, yC, xC, qpC, p.coeff + p.cs, recU, itype | 1,     \
                          p.intra_mode, ur, dl, 0);                                                                 \
     cv = te_enc_intra_c8(oV, F.osc, F.rv + yC * F.rsc + xC, F.rsc, yC, xC, qpC, p.coeff + 2 * p.cs, recV, itype | 1, \
                          p.intra_mode, ur, dl, 0);                                                                 \
-  } else if (TE_C4 && sC == 4) {                                                                                  \
+  } else if (C4 && sC == 4) {                                                                                     \
     cu = te_enc_intra_c4(F, oU, F.osc, F.ru + yC * F.rsc + xC, F.rsc, yC, xC, qpC, p.coeff + p.cs, recU, itype | 1,  \
                          p.intra_mode, ur, dl);                                                                    \
     cv = te_enc_intra_c4(F, oV, F.osc, F.rv + yC * F.rsc + xC, F.rsc, yC, xC, qpC, p.coeff + 2 * p.cs, recV,        \
@@ -884,10 +913,12 @@ TE_FN int te_encode_block_t(const TeFrame &F_, TeBits &b_, TeBlockInfo &bi_, TeP
     cv = fn(F, oV, F.osc, F.rv + yC * F.rsc + xC, F.rsc, yC, xC, sC, qpC, S.pb, p.coeff + 2 * p.cs, recV,          \
             itype | 1, tb_split && size > 8, p.intra_mode, ur, dl, p.ts);                                          \
   }
-    if constexpr (IFR) {
-      TE_INTRA_CHAINS(te_enc_intra_comp)
+    if (rq) {
+      TE_INTRA_CHAINS(te_enc_intra_comp_rq, 0)
+    } else if constexpr (IFR) {
+      TE_INTRA_CHAINS(te_enc_intra_comp, TE_C4)
     } else {
-      TE_INTRA_CHAINS(te_enc_intra_comp_nc)
+      TE_INTRA_CHAINS(te_enc_intra_comp_nc, TE_C4)
     }
 #undef TE_INTRA_CHAINS
   } else {
@@ -918,6 +949,12 @@ TE_FN int te_encode_block_t(const TeFrame &F_, TeBits &b_, TeBlockInfo &bi_, TeP
     if (mode != TE_SKIP) {
       if (zero_block) {
         te_copy_bytes(bi.rec, S.pb, size * size + 2 * sC * sC);
+      } else if (rq) {
+        cy = te_enc_inter_comp_rq(F, oY, F.osy, size, qpY, S.pb, p.coeff, recY, itype | 0, tb_split, p.ts);
+        cu = te_enc_inter_comp_rq(F, oU, F.osc, sC, qpC, te_pu(S.pb, size), p.coeff + p.cs, recU, itype | 1,
+                                  tb_split && size > 8, p.ts);
+        cv = te_enc_inter_comp_rq(F, oV, F.osc, sC, qpC, te_pv(S.pb, size), p.coeff + 2 * p.cs, recV, itype | 1,
+                                  tb_split && size > 8, p.ts);
       } else {
         if (TE_C4 && size == 8 && !tb_split)
           cy = te_enc_inter_c8(oY, F.osy, qpY, S.pb, p.coeff, recY, itype | 0);

@@ -123,14 +123,14 @@ __global__ __launch_bounds__(64) void k_l2_top_left(const uint8_t *__restrict__ 
   }
 }
 __global__ __launch_bounds__(64) void k_l2_quant(const int16_t *__restrict__ in, int16_t *__restrict__ out, int qp,
-                                                 int size, int type, int *cbp_out) {
-  // quantize, enc/encode_block.c:75-172 (rdoq 0, RDOQ light): in / out q x q raster
+                                                 int size, int type, int rdoq, int *cbp_out) {
+  // quantize, enc/encode_block.c:75-482 (RDOQ light; rdoq 1: full RDOQ, te_rdoq): in / out q x q raster
   __shared__ TeTx X;
   te_load_zig();
   const int q = size < 16 ? size : 16;
   for (int e = threadIdx.x; e < q * q; e += 64) X.C[e] = in[e];
   te_sync();
-  const int cbp = te_quant(X, qp, size, type);
+  const int cbp = te_quant(X, qp, size, type, rdoq);
   for (int e = threadIdx.x; e < q * q; e += 64) out[e] = X.C[e];
   if (threadIdx.x == 0) *cbp_out = cbp;
 }
@@ -283,10 +283,10 @@ void make_top_and_left(uint8_t *left, uint8_t *top, uint8_t *top_left, uint8_t *
   *top_left = h[4 * size];
 }
 
-// enc/encode_block.c:75-172
+// enc/encode_block.c:75-482
 int quantize(int16_t *coeff, int16_t *coeffq, int qp, int size, int coeff_block_type, int rdoq) {
-  if (rdoq) l2_die("quantize: rdoq 1 (full RDOQ) is not implemented by this build");
-  if (size < 4 || size > 64 || (size & (size - 1)) || qp < 0 || qp > 51) l2_die("quantize: bad arguments");
+  if (size < 4 || size > 64 || (size & (size - 1)) || qp < 0 || qp > 51 || (rdoq != 0 && rdoq != 1))
+    l2_die("quantize: bad arguments");
   std::lock_guard<std::mutex> lk(g_l2.mu);
   const int q = size < 16 ? size : 16;
   const size_t n = (size_t)q * q * 2;
@@ -295,7 +295,7 @@ int quantize(int16_t *coeff, int16_t *coeffq, int qp, int size, int coeff_block_
   uint8_t *din = g_l2.buf, *dout = din + n;
   int *dcbp = (int *)(dout + n);
   L2CHK(hipMemcpy2DAsync(din, 2 * q, coeff, 2 * (size_t)size, 2 * q, q, hipMemcpyHostToDevice, st));
-  k_l2_quant<<<1, 64, 0, st>>>((const int16_t *)din, (int16_t *)dout, qp, size, coeff_block_type, dcbp);
+  k_l2_quant<<<1, 64, 0, st>>>((const int16_t *)din, (int16_t *)dout, qp, size, coeff_block_type, rdoq, dcbp);
   L2CHK(hipGetLastError());
   int cbp = 0;
   L2CHK(hipMemcpy2DAsync(coeffq, 2 * (size_t)size, dout, 2 * q, 2 * q, q, hipMemcpyDeviceToHost, st));
