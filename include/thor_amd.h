@@ -366,10 +366,12 @@ int thor_enc_check_params(const thor_enc_params_t *p);
 typedef struct thor_enc thor_enc_t;
 thor_enc_t *thor_enc_create(const thor_enc_params_t *p, int device);
 void thor_enc_destroy(thor_enc_t *e);
-/* frames the context will code (params.num_frames after -skip) */
+/* frames the context will code: params.num_frames, the first of them input
+ * frame params.skip (the input sequence holds skip + num_frames frames) */
 int thor_enc_num_frames(const thor_enc_t *e);
-/* input frame (display order, 0 = first after -skip) the next call codes;
- * -1 when every frame is coded */
+/* input frame the next call codes: its index in the input sequence (display
+ * order, the -skip frames counted: the first frame coded is params.skip, as
+ * the reference seeks to it, enc/mainenc.c:510); -1 when every frame is coded */
 int thor_enc_next_input(const thor_enc_t *e);
 void *thor_enc_stream(thor_enc_t *e);
 /* Re-create the context's stream restricted to the CUs whose bits are set in
@@ -437,7 +439,7 @@ long long thor_enc_frame_bytes(const thor_enc_t *e, uint8_t *dst, size_t cap);
  * thor_enc_frame_bytes chunk.  stats (optional, 4 values): workers launched,
  * workers retired early (after the I frames, to free CU slots), tasks run,
  * arena words used. */
-/* input frame index (display order) of the frame `ahead` frames after the next
+/* input frame index (display order, the -skip frames counted) of the frame `ahead` frames after the next
  * one in coding order (ahead = 0: thor_enc_next_input); -1 past the end */
 int thor_enc_plan_input(const thor_enc_t *e, int ahead);
 int thor_enc_seq_begin(thor_enc_t *const *es, int n, int nframes, const uint8_t *const *in, uint8_t *const *dev,

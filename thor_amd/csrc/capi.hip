@@ -597,8 +597,11 @@ static int batch_phase_b(thor_dec *lead, const Batch &b, int pad = 1) {
     // else every chroma edge segment like luma
     const int clist = b.max_intra <= 1024;
     const int bc = clist ? (2 * b.max_intra + 3) / 4 : 0;
-    k_deblock_v<<<dim3(clist ? bv + bc : 3 * bv, n), 256, 0, st>>>(b.fb, bv, clist);
-    k_deblock_h<<<dim3(clist ? bh + bc : 3 * bh, n), 256, 0, st>>>(b.fb, bh, clist);
+    // (a frame one 8x8 block wide or high has no edge of that direction, and a P frame
+    // of it no intra CU either: nothing to launch)
+    const int gv = clist ? bv + bc : 3 * bv, gh = clist ? bh + bc : 3 * bh;
+    if (gv > 0) k_deblock_v<<<dim3(gv, n), 256, 0, st>>>(b.fb, bv, clist);
+    if (gh > 0) k_deblock_h<<<dim3(gh, n), 256, 0, st>>>(b.fb, bh, clist);
     HIPCHK(hipGetLastError());
   }
   if (b.any_clpf && b.clpf_grid > 0) {

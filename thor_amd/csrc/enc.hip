@@ -974,7 +974,7 @@ void thor_enc_destroy(thor_enc_t *e) {
 }
 
 int thor_enc_num_frames(const thor_enc_t *e) { return e ? (int)e->gop->plans.size() : THOR_ERR_ARG; }
-// input frame index (display order, after -skip) the next call codes; -1 when done
+// input frame index (display order, the -skip frames counted) the next call codes; -1 when done
 int thor_enc_next_input(const thor_enc_t *e) {
   if (!e) return THOR_ERR_ARG;
   return e->pos < e->gop->plans.size() ? e->gop->plans[e->pos].input_index : -1;
@@ -1277,8 +1277,9 @@ static int frames_begin_locked(EncPool &P, thor_enc_t *const *es, int n, const u
   {
     const int nv = ((W >> 3) - 1) * (H >> 3), nh = (W >> 3) * ((H >> 3) - 1);
     const int bv = (nv + 256 * DB_ITEMS - 1) / (256 * DB_ITEMS), bh = (nh + 256 * DB_ITEMS - 1) / (256 * DB_ITEMS);
-    k_enc_db_v<<<dim3(3 * bv, n), 256, 0, st>>>(P.jobs, bv);
-    k_enc_db_h<<<dim3(3 * bh, n), 256, 0, st>>>(P.jobs, bh);
+    // (a frame one 8x8 block wide or high has no edge of that direction: nothing to launch)
+    if (bv > 0) k_enc_db_v<<<dim3(3 * bv, n), 256, 0, st>>>(P.jobs, bv);
+    if (bh > 0) k_enc_db_h<<<dim3(3 * bh, n), 256, 0, st>>>(P.jobs, bh);
     EHIP(hipGetLastError());
   }
   if (lead->nsb_full > 0) {

@@ -42,8 +42,8 @@ static inline int te_display_to_code(int sub_gop, int i) {
 
 // One frame's plan: what encode_frame needs from main().
 struct TeFramePlan {
-  int input_index;  // frame of the input sequence (display order, after -skip)
-  int frame_num;    // frame_info.frame_num
+  int input_index;  // frame of the input sequence (display order, the -skip frames counted)
+  int frame_num;    // frame_info.frame_num = input_index - skip
   int frame_type, qp, b_level, num_ref, interp_ref, num_intra_modes;
   int ref_array[TE_GOP_MAX_REF];  // indices into the sliding window (ref[0] = most recently coded)
   int ref_fnum[TE_GOP_MAX_REF];   // frame numbers of those references when this frame is coded
@@ -104,7 +104,10 @@ struct TeGop {
     } else {
       qp = (f.frame_num % P.HQperiod) ? (int)(P.mqpP * (float)P.qp) + P.dqpP : P.qp;
     }
-    f.qp = qp < 0 ? 0 : (qp > 51 ? 51 : qp);
+    // frame_info.qp is a uint8_t (enc/mainenc.h:122): the value wraps modulo 256 before the
+    // clip of :287, so a QP that computes below 0 is coded at 51, not at 0
+    qp &= 255;
+    f.qp = qp > 51 ? 51 : qp;
     f.num_ref = f.frame_type == 0 ? 0 : (num_encoded < P.max_num_ref ? num_encoded : P.max_num_ref);
     f.interp_ref = 0;
     f.interp_a = f.interp_b = -1;
