@@ -460,6 +460,11 @@ int thor_enc_rows_profile(int device, long long *out);
  * path (THOR_ENC_LEAF8, default on) on `device` since the last call or the
  * last thor_enc_rows_profile; cleared.  Negative: a THOR_ERR_* code. */
 long long thor_enc_leaf8_count(int device);
+/* Uni-pred SKIP candidates of P / B frames that kernel ran through its fused
+ * pass -- early-skip check, prediction and SSD from one set of registers
+ * (THOR_ENC_ESFUSE, default on) -- on `device` since the last call or the last
+ * thor_enc_rows_profile; cleared.  Negative: a THOR_ERR_* code. */
+long long thor_enc_esfuse_count(int device);
 /* The last coded frame's reconstruction (deblocked, CLPF'd), host planes. */
 int thor_enc_read_recon(thor_enc_t *e, uint8_t *y, uint8_t *u, uint8_t *v);
 /* Per-superblock RD costs (parity instrumentation, tests/golden/rd_costs.npz):

@@ -161,8 +161,8 @@ __device__ __forceinline__ void te_sb_cellinfo(const TeJob &J, int k, int l) {
 
 // k_enc_rows' profile, summed over its workers across launches (100 MHz ticks): time coding SBs,
 // time waiting for a queue slot, SBs coded (thor_enc_rows_profile reads and clears it); [3]: CUs coded
-// by te_leaf8_intra (thor_enc_leaf8_count)
-__device__ unsigned long long g_te_rows_prof[4];
+// by te_leaf8_intra (thor_enc_leaf8_count); [4]: SKIP candidates run by te_skip_fused (thor_enc_esfuse_count)
+__device__ unsigned long long g_te_rows_prof[5];
 __global__ __launch_bounds__(64) TE_WPE void k_enc_rows(const TeJob *__restrict__ jobs, unsigned total, unsigned *q,
                                                  unsigned *items, TeScratchMem *scratch, unsigned *err,
                                                  unsigned long long spin_limit, int stall_row, const TeQLevels QL) {
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(64) TE_WPE void k_enc_rows(const TeJob *__restrict_
   // the worker's buffers (te_here): LDS at fixed addresses (g_te_*), global at
   // fixed offsets from its TeScratchMem
   g_te_mem = &scratch[blockIdx.x];
-  if (threadIdx.x == 0) g_te_leaf8_n = 0u;
+  if (threadIdx.x == 0) g_te_leaf8_n = g_te_esfuse_n = 0u;
   te_load_basis(g_te_tx);
   te_load_zig();
   TeSB &sb = s_sb;
@@ -339,6 +339,7 @@ __global__ __launch_bounds__(64) TE_WPE void k_enc_rows(const TeJob *__restrict_
     atomicAdd(&g_te_rows_prof[1], t_wait);
     atomicAdd(&g_te_rows_prof[2], n_sb);
     if (g_te_leaf8_n) atomicAdd(&g_te_rows_prof[3], (unsigned long long)g_te_leaf8_n);
+    if (g_te_esfuse_n) atomicAdd(&g_te_rows_prof[4], (unsigned long long)g_te_esfuse_n);
   }
 }
 
@@ -1020,6 +1021,17 @@ static int enc_leaf8_on() {
   return on;
 }
 
+// THOR_ENC_ESFUSE=0 in the environment (read once): uni-pred SKIP candidates keep the generic path
+// (check, te_encode_block, te_cost) instead of te_skip_fused -- the A/B switch of one binary, and the
+// tests' handle on both paths.
+static int enc_esfuse_on() {
+  static const int on = [] {
+    const char *v = getenv("THOR_ENC_ESFUSE");
+    return !(v && v[0] == '0' && v[1] == 0);
+  }();
+  return on;
+}
+
 // One context's frame job.  Its device setup (cells, SB dependency counters,
 // scheduler queue: k_enc_clear) runs on the batch stream `st`; its header words go to `hw` (host), which
 // the caller uploads with every context's in one copy to `hdr_dev`.
@@ -1090,6 +1102,7 @@ static int enc_prepare(thor_enc *e, const uint8_t *orig, int orig_stride, TeJob 
   F.early_skip_thr = P.early_skip_thr;
   F.es_thr = e->es_thr;
   F.leaf8 = enc_leaf8_on() && !P.rdoq;  // (te_leaf8_intra is an rdoq-0 quantiser: full RDOQ keeps the generic path)
+  F.esfuse = enc_esfuse_on();           // (a SKIP has no residual: full RDOQ does not matter)
   J.sb_words = e->sb_words;
   J.sb_nbits = e->sb_nbits;
   J.deps = e->deps;
@@ -1440,11 +1453,11 @@ int thor_enc_debug_stall(int row, int spin_ms) {
 // k_enc_rows' profile since the last call, summed over its workers (100 MHz ticks): time coding
 // SBs, time waiting for a queue slot, SBs coded; cleared.  Returns 3.
 int thor_enc_rows_profile(int device, long long *out) {
-  unsigned long long v[4] = {0, 0, 0, 0};
+  unsigned long long v[5] = {0, 0, 0, 0, 0};
   EHIP(hipSetDevice(device));
   EHIP(hipDeviceSynchronize());
   EHIP(hipMemcpyFromSymbol(v, HIP_SYMBOL(g_te_rows_prof), sizeof(v)));
-  const unsigned long long z[4] = {0, 0, 0, 0};
+  const unsigned long long z[5] = {0, 0, 0, 0, 0};
   EHIP(hipMemcpyToSymbol(HIP_SYMBOL(g_te_rows_prof), z, sizeof(z)));
   for (int i = 0; out && i < 3; i++) out[i] = (long long)v[i];
   return 3;
@@ -1458,6 +1471,17 @@ long long thor_enc_leaf8_count(int device) {
   EHIP(hipDeviceSynchronize());
   EHIP(hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_te_rows_prof), sizeof(v), 3 * sizeof(v)));
   EHIP(hipMemcpyToSymbol(HIP_SYMBOL(g_te_rows_prof), &z, sizeof(z), 3 * sizeof(z)));
+  return (long long)v;
+}
+
+// SKIP candidates k_enc_rows ran through te_skip_fused on `device` since the last call (or the last
+// thor_enc_rows_profile); cleared.
+long long thor_enc_esfuse_count(int device) {
+  unsigned long long v = 0, z = 0;
+  EHIP(hipSetDevice(device));
+  EHIP(hipDeviceSynchronize());
+  EHIP(hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_te_rows_prof), sizeof(v), 4 * sizeof(v)));
+  EHIP(hipMemcpyToSymbol(HIP_SYMBOL(g_te_rows_prof), &z, sizeof(z), 4 * sizeof(z)));
   return (long long)v;
 }
 

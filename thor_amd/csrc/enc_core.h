@@ -324,6 +324,7 @@ struct TeFrame {
   float early_skip_thr;
   int leaf8;          // device: I-frame 8x8 CUs take te_leaf8_intra (THOR_ENC_LEAF8, default on; 0 under rdoq); fills the padding
   const int *es_thr;  // early-skip thresholds [2][52][4], te_es_thresholds (host)
+  int esfuse;         // device: uni-pred SKIP candidates of full square CUs take te_skip_fused (THOR_ENC_ESFUSE, default on)
 };
 
 // ---- tables -------------------------------------------------------------------

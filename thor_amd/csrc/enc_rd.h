@@ -1037,6 +1037,12 @@ TE_FN uint32_t te_cost(const TeFrame &F, const TeBlockInfo &bi, const uint8_t *r
   TE_TR(F.frame_num, 3, ypos, xpos, size, sy, su + sv, cost);
   return cost;
 }
+#if !defined(TE_HOST)
+// A uni-pred SKIP candidate of a full square CU in one pass (defined with the early-skip check below)
+TE_NOINL long long te_skip_fused(const TeFrame &F_, TeBits &b_, TeBlockInfo &bi_, TeParam &p_, int test);
+TE_FN int te_fused_bits(long long fr) { return fr < 0 ? (int)fr : (int)(uint32_t)fr; }  // its bit count (or -1, -2)
+TE_FN uint32_t te_fused_cost(long long fr) { return (uint32_t)(fr >> 32); }               // its cost (fr >= 0)
+#endif
 
 // search orders (constant memory: local arrays indexed at run time would be
 // built on the stack on every call)
@@ -1699,14 +1705,17 @@ TE_FN void te_copy_best(TeBlockInfo &bi, TeParam &tmp) {
 }
 
 // copy_block_to_frame (:1802-1819) + copy_deblock_data (:1947-1981)
-TE_FN void te_commit_block(const TeFrame &F, const TeBlockInfo &bi) {
+// (pixels = 0: the reconstruction is in the frame already, te_skip_fused; the cells only)
+TE_FN void te_commit_block(const TeFrame &F, const TeBlockInfo &bi, int pixels = 1) {
   TE_P(TP_COMMIT);
   const int size = bi.size, bw = bi.bwidth, bh = bi.bheight, sC = size / 2;
-  uint8_t *r = bi.rec;
-  te_copy_rect(F.ry + bi.ypos * F.rsy + bi.xpos, F.rsy, r, size, bw, bh);
-  const int cw = bw / 2, ch = bh / 2, oc = (bi.ypos / 2) * F.rsc + bi.xpos / 2;
-  te_copy_rect(F.ru + oc, F.rsc, te_pu(r, size), sC, cw, ch);
-  te_copy_rect(F.rv + oc, F.rsc, te_pv(r, size), sC, cw, ch);
+  if (pixels) {
+    uint8_t *r = bi.rec;
+    te_copy_rect(F.ry + bi.ypos * F.rsy + bi.xpos, F.rsy, r, size, bw, bh);
+    const int cw = bw / 2, ch = bh / 2, oc = (bi.ypos / 2) * F.rsc + bi.xpos / 2;
+    te_copy_rect(F.ru + oc, F.rsc, te_pu(r, size), sC, cw, ch);
+    te_copy_rect(F.rv + oc, F.rsc, te_pv(r, size), sC, cw, ch);
+  }
   const TeParam &p = bi.bp;
   const int div = size / 8, bs = F.W / 4;
   const int nw = bw / 4, nh = bh / 4;
@@ -1958,8 +1967,19 @@ TE_NOINL uint32_t te_mode_decision(const TeFrame &F_, TeSB &sb_, TeBlockInfo &bi
       tmp.mv1[0] = bi.skip_c[k].mv1;
       tmp.dir = bi.skip_c[k].bipred_flag;
       tmp.mode = TE_SKIP;
-      const int nbits = te_encode_block(F, b, bi, tmp);
-      cost = te_cost(F, bi, bi.rec, bi.bwidth, bi.bheight, nbits);
+      int nbits = -2;
+#if !defined(TE_HOST)
+      // a uni-pred candidate of a full square CU: prediction, SSD and syntax in one pass (no thresholds)
+      if (te_uni(F.esfuse && !rectangular && tmp.dir != 2)) {
+        const long long fr = te_skip_fused(F, b, bi, tmp, 0);
+        nbits = te_fused_bits(fr);
+        cost = te_fused_cost(fr);
+      }
+#endif
+      if (nbits == -2) {
+        nbits = te_encode_block(F, b, bi, tmp);
+        cost = te_cost(F, bi, bi.rec, bi.bwidth, bi.bheight, nbits);
+      }
       if (cost < min_cost) {
         min_cost = cost;
         te_copy_best(bi, tmp);
@@ -2432,6 +2452,159 @@ TE_FN int te_es_chroma_mc(const uint8_t *ref, int rs, TeMv mv, int sign, const u
   }
   return te_any(flag);
 }
+
+// ---- a uni-pred SKIP candidate in one pass -----------------------------------
+// A SKIP candidate's reconstruction is its prediction, and the early-skip check
+// above already holds that prediction in registers, unit by unit.  The generic
+// path throws it away, predicts the CU again into bi.rec (te_encode_block ->
+// te_pred_yuv) and reads it back with the original for three SSD passes
+// (te_cost).  Here the check's units also go to bi.rec and into per-lane SSD
+// sums: luma as te_es_luma_mc (one 4x4 unit per lane of the size0 = min(size, 32)
+// sub-block), chroma as whole s0c x s0c blocks -- U's units on lanes
+// 0..nuc-1, V's on lanes nuc..2 nuc-1 -- from which the column sums
+// te_es_chroma_mc tests are derived.  Then write_block and cost_calc's
+// expression (te_cost's), with te_encode_block's and te_cost's trace records.
+// `test` = 0: no thresholds (te_mode_decision's SKIP candidates); 1: with them;
+// 3: with them, and the units stored straight into the frame's planes instead
+// of bi.rec (the CU's only candidate: if it passes it is what te_commit_block
+// would copy there, and if it fails the mode decision or the smaller CUs that
+// follow commit over the whole block; nothing reads a CU's reconstruction
+// before its commit, and other workers wait for the SB's flag).  The one
+// vector used is te_pred_yuv's, clipped for `size`; the check clips for size0,
+// which differs only for vectors that reach 80 px outside the frame with
+// size 64: then (-2) the caller takes the generic path.
+// Returns cost << 32 | bit count (te_fused_cost, te_fused_bits); -1: a threshold test failed (bi.rec
+// holds part of a candidate the next one overwrites); -2: not applicable.
+__shared__ unsigned g_te_esfuse_n;  // candidates this worker ran here (k_enc_rows sums it into its profile)
+TE_NOINL long long te_skip_fused(const TeFrame &F_, TeBits &b_, TeBlockInfo &bi_, TeParam &p_, int test) {
+  const TeFrame &F = *te_lds(&F_);
+  const TeScratch S = te_here();
+  TeBlockInfo &bi = *te_lds(&bi_);
+  TeParam &p = *te_lds(&p_);
+  TeTx &X = *S.tx;
+  const int size = bi.size, ypos = bi.ypos, xpos = bi.xpos, size0 = TE_MIN(size, 32), s0c = size0 / 2, sC = size / 2;
+  const int r = p.ref_idx0, sign = F.ref_fnum[r] > F.frame_num, bip = F.enable_bipred;
+  const TeMv mv = te_clip_mv(p.mv0[0], ypos, xpos, F.W, F.H, size, sign);
+  int thr_y = 0, thr_c = 0;
+  if (test) {
+    const TeMv m0 = te_clip_mv(p.mv0[0], ypos, xpos, F.W, F.H, size0, sign);
+    if (te_uni(m0.x != mv.x || m0.y != mv.y)) return -2;
+    const int qpY = F.qp + bi.delta_qp, qpC = te_chroma_qp(qpY);
+    const int *T = F.es_thr + ((F.speed > 1 && size == 64) ? 52 * 4 : 0);  // (as te_check_early_skip)
+    thr_y = T[qpY * 4 + (size0 == 8 ? 0 : (size0 == 16 ? 1 : 2))];
+    thr_c = T[qpC * 4 + 3];
+  }
+  if (TE_LANE == 0) atomicAdd(&g_te_esfuse_n, 1u);
+  const int mx = sign ? -mv.x : mv.x, my = sign ? -mv.y : mv.y;
+  const int w4 = size0 >> 2, s2 = size0 >> 1, w4c = s0c >> 2, nuc = w4c * w4c;
+  // the lane's luma unit, and its chroma unit: plane pl (0 U, 1 V), unit uc
+  const int i0 = te_dv(TE_LANE, w4) * 4, j0 = (TE_LANE - te_dv(TE_LANE, w4) * w4) * 4;
+  const int pl = TE_LANE >= nuc, uc = TE_LANE - (pl ? nuc : 0);
+  const int ci0 = te_dv(uc, w4c) * 4, cj0 = (uc - te_dv(uc, w4c) * w4c) * 4;
+  // where the units go: the candidate buffer (every level's is global memory, compact Y | U | V), or -- the
+  // CU's only candidate, whose passing prediction is what gets committed -- the frame's planes at the CU
+  const int direct = test & 2;
+  test &= 1;
+  uint8_t *const dy = te_glb(direct ? F.ry + ypos * F.rsy + xpos : bi.rec);
+  uint8_t *const dc = te_glb(direct ? (pl ? F.rv : F.ru) + (ypos / 2) * F.rsc + xpos / 2
+                                    : (pl ? te_pv(bi.rec, size) : te_pu(bi.rec, size)));
+  const int dsy = direct ? F.rsy : size, dsc = direct ? F.rsc : sC;
+  // per-lane SSD sums as te_ssd's: sum a^2 + sum b^2, and sum ab (luma; U and V together)
+  uint32_t qy = 0, aby = 0, qc = 0, abc = 0;
+  {
+    TE_P(TP_ES_CHECK);
+    for (int i = 0; i < size; i += size0)
+      for (int j = 0; j < size; j += size0) {
+        if (TE_LANE < w4 * w4) {
+          const uint8_t *org = F.oy + (ypos + i) * F.osy + xpos + j;
+          const uint8_t *rf = F.refy[r] + (ypos + i + (my >> 2)) * F.rsy + xpos + j + (mx >> 2);
+          uint32_t ov[4];
+#pragma unroll
+          for (int y = 0; y < 4; y++) ov[y] = te_ld4(org + (i0 + y) * F.osy + j0);
+          int o[4][4];
+          te_mc_luma_unit(rf, F.rsy, i0, j0, mx & 3, my & 3, bip, o);
+          uint8_t *d = dy + (i + i0) * dsy + j + j0;
+#pragma unroll
+          for (int y = 0; y < 4; y++) {
+            const uint32_t pw = te_pack4(o[y][0], o[y][1], o[y][2], o[y][3]);
+            te_st4(d + y * dsy, pw);
+            qy = te_dot4(pw, pw, te_dot4(ov[y], ov[y], qy));
+            aby = te_dot4(ov[y], pw, aby);
+          }
+          if (test) {
+#pragma unroll
+            for (int a = 0; a < 2; a++)
+#pragma unroll
+              for (int b = 0; b < 2; b++) {
+                const int y = 2 * a, x = 2 * b;
+                const int s = te_b(ov[y], x) - o[y][x] + te_b(ov[y], x + 1) - o[y][x + 1] + te_b(ov[y + 1], x) -
+                              o[y + 1][x] + te_b(ov[y + 1], x + 1) - o[y + 1][x + 1];
+                X.R[(i0 / 2 + a) * s2 + j0 / 2 + b] = (int16_t)((s + 2) >> 2);
+              }
+          }
+        }
+        if (test) {
+          te_sync();
+          te_fwd_tx(X, s2, 0);
+          int flag = 0;
+          for (int e = TE_LANE; e < s2 * s2; e += TE_NL) flag |= te_abs(X.C[e]) > thr_y;
+          if (te_any(flag)) return -1;
+        }
+        int cs[4] = {0, 0, 0, 0};  // the lane's chroma unit: column sums of org - pred over its 4 rows
+        if (TE_LANE < 2 * nuc) {
+          const int oc = ((ypos + i) / 2) * F.osc + (xpos + j) / 2;
+          const int rc = ((ypos + i) / 2 + (my >> 3)) * F.rsc + (xpos + j) / 2 + (mx >> 3);
+          const uint8_t *org = (pl ? F.ov : F.ou) + oc;
+          const uint8_t *rf = (pl ? F.refv[r] : F.refu[r]) + rc;
+          uint32_t ov[4];
+#pragma unroll
+          for (int y = 0; y < 4; y++) ov[y] = te_ld4(org + (ci0 + y) * F.osc + cj0);
+          int o[4][4];
+          te_mc_chroma_unit(rf, F.rsc, ci0, cj0, mx & 7, my & 7, o);
+          uint8_t *d = dc + (i / 2 + ci0) * dsc + j / 2 + cj0;
+#pragma unroll
+          for (int y = 0; y < 4; y++) {
+            const uint32_t pw = te_pack4(o[y][0], o[y][1], o[y][2], o[y][3]);
+            te_st4(d + y * dsc, pw);
+            qc = te_dot4(pw, pw, te_dot4(ov[y], ov[y], qc));
+            abc = te_dot4(ov[y], pw, abc);
+          }
+#pragma unroll
+          for (int x = 0; x < 4; x++)
+#pragma unroll
+            for (int y = 0; y < 4; y++) cs[x] += te_b(ov[y], x) - o[y][x];
+        }
+        if (test) {
+          int flag = 0;
+          if (s0c == 8) {  // every column over 8 rows: the bottom units' sums join the top ones' (lane ^ 2 within a quad)
+#pragma unroll
+            for (int x = 0; x < 4; x++) {
+              const int tot = cs[x] + TE_DPP(cs[x], 0x4E);
+              if (TE_LANE < 2 * nuc && uc < 2) flag |= te_wrap16(tot) > (int)(int16_t)thr_c;
+            }
+          } else if (TE_LANE < 2 * nuc && uc == 0) {  // the top-left 4x4, column pairs
+            flag = (cs[0] + cs[1] > thr_c) | (cs[2] + cs[3] > thr_c);
+          }
+          if (te_any(flag)) return -1;
+        }
+      }
+  }
+  te_sync();
+  const uint32_t sy = te_sum(qy - 2u * aby), sc = te_sum(qc - 2u * abc);
+  // encode_block's SKIP leg: no residual, then the syntax
+  p.mode = TE_SKIP;
+  p.tb_split = 0;
+  p.cbp_y = p.cbp_u = p.cbp_v = 0;
+  const int nbits = te_write_block(b_, F_, bi_, p_, X.scan);
+  TE_TR(F.frame_num, 2, ypos, xpos, size | TE_SKIP << 8 | (p.tb_param + 1) << 12 | p.skip_idx << 16,
+        p.ref_idx0 | p.ref_idx1 << 4 | p.pb_part << 8 | p.intra_mode << 12, nbits, 0);
+  // cost_calc (te_cost's expression)
+  const double prod = F.lambda * (double)nbits;
+  uint32_t cost = sy + sc + (uint32_t)(int32_t)(prod + 0.5);
+  if (cost > (1u << 30)) cost = 1u << 30;
+  TE_TR(F.frame_num, 3, ypos, xpos, size, sy, sc, cost);
+  return (long long)cost << 32 | (long long)nbits;
+}
 #endif
 
 // check_early_skip_sub_blockC (:2540-2611): column sums of the residual
@@ -2518,7 +2691,9 @@ int te_check_early_skip(const TeFrame &F_, const TeBlockInfo &bi_, const TeParam
   return 1;
 }
 
-// search_early_skip_candidates, :2743-2783
+// search_early_skip_candidates, :2743-2783.  Returns 0: no candidate passed; 1: the best one is in
+// bi.rec_best; 3: the CU's only candidate passed and its reconstruction is in the frame already
+// (te_skip_fused's direct store: te_commit_block then writes the cells only).
 TE_NOINL int te_search_early_skip(const TeFrame &F_, TeSB &sb_, TeBlockInfo &bi_, int16_t *tmp_coef,
                                   uint32_t *best_cost) {
   const TeFrame &F = *te_lds(&F_);
@@ -2542,16 +2717,30 @@ TE_NOINL int te_search_early_skip(const TeFrame &F_, TeSB &sb_, TeBlockInfo &bi_
     tmp.mv0[0] = bi.skip_c[k].mv0;
     tmp.mv1[0] = bi.skip_c[k].mv1;
     tmp.dir = bi.skip_c[k].bipred_flag;
-    if (te_check_early_skip(F, bi, tmp)) {
-      early = 1;
+    // a uni-pred candidate: check, prediction, SSD and syntax in one pass (te_skip_fused; wave-uniform)
+    int nbits = -2;
+    uint32_t cost = 0;
+#if !defined(TE_HOST)
+    if (te_uni(F.esfuse && tmp.dir != 2)) {
+      const int direct = bi.num_skip == 1 && !F.enable_tb_split;
+      const long long fr = te_skip_fused(F, sb.bits, bi, tmp, direct ? 3 : 1);
+      nbits = te_fused_bits(fr);
+      cost = te_fused_cost(fr);
+      if (direct && nbits >= 0) early = 2;  // (the reconstruction is in the frame already)
+    }
+#endif
+    if (nbits == -2) {
+      if (!te_check_early_skip(F, bi, tmp)) continue;
       tmp.mode = TE_SKIP;
-      const int nbits = te_encode_block(F, sb.bits, bi, tmp);
-      const uint32_t cost = te_cost(F, bi, bi.rec, bi.size, bi.size, nbits);
-      if (cost < min_cost) {
-        min_cost = cost;
-        te_copy_best(bi, tmp);
-        te_keep_best_bits(sb.bits, bi, nbits);
-      }
+      nbits = te_encode_block(F, sb.bits, bi, tmp);
+      cost = te_cost(F, bi, bi.rec, bi.size, bi.size, nbits);
+    }
+    if (nbits < 0) continue;  // (the fused pass's check failed)
+    early |= 1;
+    if (cost < min_cost) {
+      min_cost = cost;
+      te_copy_best(bi, tmp);
+      te_keep_best_bits(sb.bits, bi, nbits);
     }
   }
   *best_cost = min_cost;
@@ -2810,7 +2999,7 @@ TE_FN uint32_t te_process_block_b(const TeFrame &F_, TeSB &sb_, int ypos, int xp
       bi.bp.tb_param = 0;
       const int nbit = te_encode_final(F, b, bi);
       cost = same ? es_cost : te_cost(F, bi, bi.rec, SIZE, SIZE, nbit);
-      te_commit_block(F, bi);
+      te_commit_block(F, bi, !(early & 2));  // (early & 2: the only candidate went straight to the frame; then `same`)
       return cost;
     }
   }
