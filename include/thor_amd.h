@@ -574,6 +574,56 @@ int thor_ti_read_fields(thor_ti_t *t, int level, int16_t *mv0, int16_t *mv1);
 /* THOR_OK, or THOR_ERR_HIP if a search wavefront wait gave up (then cleared). */
 int thor_ti_status(thor_ti_t *t);
 
+/* ---- frame quality: sum of squared errors / PSNR on the device ------------ *
+ * What the reference prints per coded frame (snr_yuv, common/snr.c:32-89,
+ * enc/mainenc.c:522-540), computed where the frames live: two reads of each
+ * frame in HBM, three 64-bit sums out (k_sse_i420, thor_amd/csrc/quality.hip).
+ * The sums are exact integers: the same on every run and every launch shape.
+ *
+ * sse[3*i + {0,1,2}] = sum (a - b)^2 over the Y (width x height), U, V
+ * ((width>>1) x (height>>1)) planes of frame pair i.  a / b: HOST arrays of n
+ * plane sets (DEVICE pointers, own strides, any alignment; 16-byte aligned
+ * pointers and strides take 16-byte loads); sse: DEVICE, 3*n uint64,
+ * overwritten.  Enqueued on `stream`; returns without waiting. */
+int thor_sse_i420(const thor_yuv_planes_t *a, const thor_yuv_planes_t *b, int n, int width, int height,
+                  uint64_t *sse, void *stream);
+/* -10*log10(sse / (65025.0 * height * width)) exactly as common/snr.c:60-61
+ * evaluates it (double; sse 0 -> +inf).  For a chroma plane pass its size,
+ * (width>>1, height>>1). */
+double thor_psnr(uint64_t sse, int width, int height);
+/* The decoder's resident frame `frame_num` against `orig` (DEVICE planes, own
+ * strides): the three sums into sse_dev (DEVICE, 3 uint64, overwritten), by the
+ * same kernel, enqueued on the context's stream after the work already queued
+ * there (the frame's decode included); returns without waiting.  THOR_ERR_REF
+ * when the frame is not resident. */
+int thor_dec_frame_sse(thor_dec_t *d, int frame_num, const thor_yuv_planes_t *orig, uint64_t *sse_dev);
+/* Encoder, per-frame batches (thor_enc_frame / thor_enc_frames / _begin / _end).
+ * thor_enc_measure_sse(e, 1): from the next frame on, every batch with at least
+ * one measuring context enqueues ONE launch of the kernel for its measuring
+ * contexts, after the frame's last stage that writes the reconstruction's
+ * interior (CLPF, or deblocking, or the RD loop when both are off): the input
+ * frame (orig[i], orig_stride[i]) against the final reconstruction in its slot.
+ * The sums travel with the coded words: read back by thor_enc_frames_end
+ * (double-buffered like the arena, so two batches may be in flight), dropped
+ * with a dropped batch -- a context rolled back keeps, with its chunk, the
+ * sums of the last frame it ended.  Default off, and off means off: with no
+ * measuring context a batch gets no launch, allocation or copy.  THOR_ERR_ARG
+ * with a batch or a sequence launch in flight on the context.
+ * params.snrcalc stays inert: it defaults to 1 (the reference's default), so
+ * honouring it would put a launch into every existing caller's batches; the
+ * switch is this call.
+ * thor_enc_frame_sse: the last ended frame's Y, U, V sums; THOR_ERR_ARG when
+ * measurement is off or no frame was ended with it on. */
+int thor_enc_measure_sse(thor_enc_t *e, int on);
+int thor_enc_frame_sse(const thor_enc_t *e, uint64_t sse[3]);
+/* Sequence launch: a measuring context's frames add each superblock row's
+ * squared errors to the frame's sums inside the launch, once the row is final
+ * (its FIN task) -- the reconstructions the launch overwrites are measured
+ * before they go.  Frame f of context i of the last ended launch; valid after
+ * thor_enc_seq_end, until the next thor_enc_seq_begin on the device.
+ * THOR_ERR_ARG when that context was not measuring. */
+int thor_enc_seq_sse(thor_enc_t *e0, int i, int f, uint64_t sse[3]);
+
 /* ---- device memory helpers (so the C-ABI is usable without torch) ------ */
 void *thor_dev_alloc(size_t bytes);
 int thor_dev_free(void *p);

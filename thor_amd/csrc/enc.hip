@@ -14,6 +14,8 @@
 //   k_enc_db_v/h    deblocking of every job's frame (the decoder's bodies, loopfilter.hip)
 //   k_enc_clpf      CLPF decision per full SB (clpf_decision, enc/encode_frame.c:50-63)
 //                   and CLPF of the flagged ones, one 8x8 block per lane
+//   k_sse_i420      (thor_enc_measure_sse only) the measuring contexts' input frames
+//                   against their final reconstructions (quality.hip)
 //   k_enc_pad       padding (the decoder's body)
 //   k_enc_pack      frame header + SB bit strings + CLPF bits -> the frame's
 //                   bytes (putbits / flush_all_bits, enc/putbits.c:57-129),
@@ -739,6 +741,10 @@ struct thor_enc {
   int last_slot, last_frame_num;
   std::vector<uint8_t> chunk;  // 4-byte length + bytes of the last frame
   bool first;
+  // frame quality (thor_enc_measure_sse): the last ended frame's Y, U, V sums of squared errors
+  int measure;
+  bool sse_valid;
+  uint64_t sse[3];
 };
 
 static int enc_alloc(thor_enc *e) {
@@ -805,12 +811,18 @@ struct EncPool {
   int *meta[2] = {nullptr, nullptr};
   unsigned long long *arena_ctr = nullptr;
   hipEvent_t ev[2] = {nullptr, nullptr};
+  // frame quality (thor_enc_measure_sse; allocated by the first batch with a measuring context):
+  // the measuring contexts' plane pairs (page-locked staging per batch buffer -> device), the
+  // kernel's sums (device) and their page-locked copies per batch buffer, read in _end
+  SsePair *sse_pairs = nullptr, *sse_pairs_host[2] = {nullptr, nullptr};
+  unsigned long long *sse_dev = nullptr, *sse_host[2] = {nullptr, nullptr};
   // batches begun and not yet ended (thor_enc_frames_begin / _end), oldest first
   struct Pending {
     std::vector<thor_enc *> es;
     std::vector<int> cur;        // the slot each context coded into
     std::vector<uint32_t *> words;  // the output buffer each context packed into
     std::vector<int> frame_num;
+    std::vector<int> sse_idx;    // each context's place among the measuring ones (-1: not measuring); empty: none measures
     int buf;                     // jobs_host / hdr_host / arena / meta / ev index
     hipStream_t st;
     // each context's state before the batch (restored when the batch fails)
@@ -886,6 +898,18 @@ static int pool_reserve(EncPool &P, size_t nwork, size_t scan_n, size_t nsb_tota
     EHIP(hipMalloc(&P.scan, scan_n * sizeof(long long)));
     P.scan_n = scan_n;
   }
+  return THOR_OK;
+}
+
+// the pool's frame-quality buffers, on first use (the caller holds P.mu and has made P's device current)
+static int pool_reserve_sse(EncPool &P) {
+  if (P.sse_dev) return THOR_OK;
+  EHIP(hipMalloc(&P.sse_pairs, THOR_ENC_MAX_BATCH * sizeof(SsePair)));
+  for (int b = 0; b < 2; b++) {
+    EHIP(hipHostMalloc((void **)&P.sse_pairs_host[b], THOR_ENC_MAX_BATCH * sizeof(SsePair), hipHostMallocDefault));
+    EHIP(hipHostMalloc((void **)&P.sse_host[b], THOR_ENC_MAX_BATCH * 3 * sizeof(unsigned long long), hipHostMallocDefault));
+  }
+  EHIP(hipMalloc(&P.sse_dev, THOR_ENC_MAX_BATCH * 3 * sizeof(unsigned long long)));
   return THOR_OK;
 }
 
@@ -1203,6 +1227,9 @@ static int frames_begin_locked(EncPool &P, thor_enc_t *const *es, int n, const u
   int rc = pool_reserve(P, (size_t)(nwork < TE_MAX_WORKERS ? nwork : TE_MAX_WORKERS), (size_t)n * (lead->nsb + 1),
                         (size_t)n * lead->nsb);
   if (rc != THOR_OK) return rc;
+  int nmeas = 0;
+  for (int i = 0; i < n; i++) nmeas += es[i]->measure != 0;
+  if (nmeas && (rc = pool_reserve_sse(P)) != THOR_OK) return rc;
   hipStream_t st = lead->stream;
   // the pool's workers and scratch are shared: a batch on another stream first waits for the pending ones
   for (const EncPool::Pending &q : P.pending)
@@ -1299,6 +1326,26 @@ static int frames_begin_locked(EncPool &P, thor_enc_t *const *es, int n, const u
     k_enc_clpf<<<dim3(lead->nsb_full, n), 64, 0, st>>>(P.jobs);
     EHIP(hipGetLastError());
   }
+  // Frame quality: one k_sse_i420 launch for the batch's measuring contexts, each input frame against
+  // its final reconstruction.  Every writer of the slot's interior is behind us in stream order (the RD
+  // loop, deblocking, CLPF; the padding below writes only outside it), so the launch goes here whichever
+  // of the filters ran.  The sums follow into this batch buffer's page-locked copy; _end reads them
+  // once the batch's event has passed.
+  std::vector<int> sse_idx;
+  if (nmeas) {
+    SsePair *hp = P.sse_pairs_host[buf];
+    sse_idx.assign(n, -1);
+    int m = 0;
+    for (int i = 0; i < n; i++) {
+      if (!es[i]->measure) continue;
+      const TeFrame &F = jobs[i].F;
+      hp[m] = SsePair{{F.oy, F.ou, F.ov}, {F.ry, F.ru, F.rv}, {F.osy, F.osc}, {F.rsy, F.rsc}};
+      sse_idx[i] = m++;
+    }
+    EHIP(hipMemcpyAsync(P.sse_pairs, hp, (size_t)m * sizeof(SsePair), hipMemcpyHostToDevice, st));
+    if ((rc = sse_enqueue(P.sse_pairs, nullptr, m, W, H, P.sse_dev, st)) != THOR_OK) return rc;
+    EHIP(hipMemcpyAsync(P.sse_host[buf], P.sse_dev, (size_t)m * 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  }
   k_enc_pad<<<dim3((pad_chunks(W, H) + 255) / 256, n), 256, 0, st>>>(P.jobs);
   EHIP(hipGetLastError());
   // the packed frames straight into the host arena, their sizes into the meta words; an event behind
@@ -1310,6 +1357,7 @@ static int frames_begin_locked(EncPool &P, thor_enc_t *const *es, int n, const u
   EncPool::Pending q;
   q.buf = buf;
   q.st = st;
+  q.sse_idx = std::move(sse_idx);
   for (int i = 0; i < n; i++) {
     thor_enc *e = es[i];
     q.snap.push_back({e->pos, e->first, e->last_slot, e->last_frame_num, e->opar, e->slot_of_window});
@@ -1397,6 +1445,10 @@ static int frames_end_locked(EncPool &P, thor_enc_t *const *es, int n) {
       for (size_t b = 0; b < nb; b++) e->chunk[4 + b] = (uint8_t)(tmp[b >> 2] >> (24 - 8 * (b & 3)));
       P.arena_want[q.buf] = 2 * P.arena_words[q.buf];
     }
+    // the frame's sums, with its chunk (a dropped batch never gets here: the context then keeps both
+    // from the last frame it ended)
+    e->sse_valid = !q.sse_idx.empty() && q.sse_idx[i] >= 0;
+    for (int c = 0; c < 3; c++) e->sse[c] = e->sse_valid ? (uint64_t)P.sse_host[q.buf][3 * q.sse_idx[i] + c] : 0;
   }
   return THOR_OK;
 }
@@ -1438,6 +1490,29 @@ int thor_enc_reset(thor_enc_t *e) {
   e->last_frame_num = -1;
   e->slot_of_window.assign(33, -1);
   e->chunk.clear();
+  e->sse_valid = false;
+  return THOR_OK;
+}
+
+// Frame quality of the per-frame batches: from the next frame on (on = 1) every batch measures this
+// context's input frame against its final reconstruction (frames_begin_locked).  Not with a batch or
+// a sequence launch in flight on the context: a frame begun keeps the setting it was begun with.
+int thor_enc_measure_sse(thor_enc_t *e, int on) {
+  if (!e || ts_member(e)) return THOR_ERR_ARG;
+  EncPool &P = pool_for(e->device);
+  std::lock_guard<std::mutex> lk(P.mu);
+  for (const EncPool::Pending &q : P.pending)
+    for (thor_enc *x : q.es)
+      if (x == e) return THOR_ERR_ARG;
+  e->measure = on != 0;
+  if (!on) e->sse_valid = false;
+  return THOR_OK;
+}
+
+// The last ended frame's sums of squared errors (Y, U, V).
+int thor_enc_frame_sse(const thor_enc_t *e, uint64_t sse[3]) {
+  if (!e || !sse || !e->measure || !e->sse_valid) return THOR_ERR_ARG;
+  for (int c = 0; c < 3; c++) sse[c] = e->sse[c];
   return THOR_OK;
 }
 

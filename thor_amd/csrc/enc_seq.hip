@@ -66,6 +66,7 @@ struct TsJob {
   int cls, aux, need0, is_i;  // queue class of the job's RD tasks / of its other tasks
   uint8_t *cy, *cu, *cv;     // the reconstruction (loop filters, padding)
   int sy, sc, qp, qpc, deblock;
+  unsigned long long *sse;   // the frame's Y, U, V sums of squared errors (thor_enc_measure_sse), nullptr: not measured
 };
 struct TsArgs {
   const TsJob *jobs;
@@ -157,6 +158,28 @@ __device__ void ts_copy_range(uint8_t *dst, const uint8_t *src, long long a, lon
   }
 }
 
+// Frame quality (thor_enc_measure_sse): SB row k's squared errors -- the input frame against the
+// reconstruction -- added to the job's three 64-bit sums, by FIN(k)'s wave once the row's CLPF is done.
+// The rows are final there.  From the rules above, the tasks that write pixels of luma rows
+// [64k, 64k + 64) (and the chroma rows under them) are:
+//   RD(k, *)   the reconstruction itself -- all done before DBV(k) is queued;
+//   DBV(k)     the row's vertical edges (a vertical edge changes pixels of its own rows only);
+//   DBH(k)     horizontal edges at rows 64k .. 64k + 56, each reaching a few rows up and down: after
+//              DBV(k - 1) and DBV(k);
+//   DBH(k + 1) its first edge, at row 64(k + 1), reaches up into this row's last rows;
+//   FIN(k)     the CLPF of the row's full SBs (an SB reads and writes nothing outside itself), and the
+//              padding, which writes only outside the interior.
+// FIN(k) is queued by the second of DBH(k) and DBH(k + 1) (the last row: by DBH(k) alone), so every
+// other writer is behind it, and no FIN of another row, nor any task of a later frame, touches these
+// pixels until the slot leaves the window.  The frame's FIN tasks are all done before its PACK, and the
+// launch before the host reads the sums.
+// Out of line behind the per-job flag: the flag-off path of FIN is one uniform branch.
+__device__ __noinline__ void ts_sse_row(const TsJob &T, int k) {
+  const TeFrame &F = T.J.F;
+  const SsePair P = {{F.oy, F.ou, F.ov}, {T.cy, T.cu, T.cv}, {F.osy, F.osc}, {T.sy, T.sc}};
+  sse_wave_band(P, F.W, F.H, k * 64, min(k * 64 + 64, F.H), T.sse);
+}
+
 // The tasks other than RD (FETCH, DBV, DBH, FIN, PACK), out of line: k_enc_seq's
 // RD path keeps the register allocation k_enc_rows has (the task bodies inlined
 // beside te_encode_sb cost the P-frame SBs a third more time).
@@ -221,6 +244,7 @@ __device__ __noinline__ void ts_aux(const TsArgs &A, int j, int type, int idx) {
       }
     }
     te_sync();
+    if (T.sse) ts_sse_row(T, k);  // the row is final (see ts_sse_row)
     {  // padding of the row's pixels (and the top / bottom pad rows at the frame's ends)
       const int r0 = k * 64, r1 = min(k * 64 + 64, H);
       const PadPlane py(T.cy, T.sy, W, H, THOR_PAD_Y, r0, r1);
@@ -455,6 +479,8 @@ struct TsRun {  // one sequence launch in flight on a device
   hipEvent_t ev = nullptr;
   std::vector<EncPool::Pending::Snap> snap;
   std::vector<std::vector<int>> frame_num;  // [i][f]
+  std::vector<int> measure;                 // [i]: the context was measuring (thor_enc_measure_sse)
+  std::vector<unsigned long long> sse;      // [i][f][3], read back by thor_enc_seq_end (empty: none measured)
 };
 struct TsPool {  // per device: the sequence launch's buffers (grown, never shrunk)
   TsJob *jobs = nullptr;
@@ -470,6 +496,8 @@ struct TsPool {  // per device: the sequence launch's buffers (grown, never shru
   size_t arena_words = 0;
   int *meta = nullptr;        // host, page-locked
   size_t nmeta = 0;
+  unsigned long long *sse = nullptr;  // device: [job][3] sums of squared errors (measuring contexts only use theirs)
+  size_t nsse = 0;
   int max_workers = 0;
   long long prof[TS_NPROF] = {};
   TsRun run;
@@ -575,6 +603,9 @@ int thor_enc_seq_begin(thor_enc_t *const *es, int n, int nframes, const uint8_t 
   if ((rc = ts_grow_dev(&S.cnt, S.ncnt, (size_t)njobs * per_cnt)) != THOR_OK) return rc;
   if ((rc = ts_grow_dev(&S.hdr, S.nhdr, (size_t)njobs * 64)) != THOR_OK) return rc;
   if (!S.ctl) EHIP(hipMalloc(&S.ctl, TS_CTL_WORDS * sizeof(unsigned)));
+  int nmeas = 0;
+  for (int i = 0; i < n; i++) nmeas += es[i]->measure != 0;
+  if (nmeas && (rc = ts_grow_dev(&S.sse, S.nsse, (size_t)njobs * 3)) != THOR_OK) return rc;
   if ((size_t)njobs * 2 > S.nmeta) {
     if (S.meta) (void)hipHostFree(S.meta);
     S.meta = nullptr;
@@ -613,6 +644,7 @@ int thor_enc_seq_begin(thor_enc_t *const *es, int n, int nframes, const uint8_t 
     thor_enc *e = es[i];
     run.snap.push_back({e->pos, e->first, e->last_slot, e->last_frame_num, e->opar, e->slot_of_window});
     run.es.push_back(e);
+    run.measure.push_back(e->measure);
   }
   auto restore = [&]() {
     for (int i = 0; i < n; i++) {
@@ -674,6 +706,7 @@ int thor_enc_seq_begin(thor_enc_t *const *es, int n, int nframes, const uint8_t 
       T.qp = pl.qp;
       T.qpc = chroma_qp_host(pl.qp);
       T.deblock = e->p.deblocking;
+      T.sse = e->measure ? S.sse + (size_t)jx * 3 : nullptr;
       run.frame_num[i][f] = pl.frame_num;
       // tasks of the job: RD nsb, DBV / DBH / FIN nsbv each, PACK 1 (+ FETCH nsbv)
       qn[T.cls] += nsb;
@@ -732,6 +765,7 @@ int thor_enc_seq_begin(thor_enc_t *const *es, int n, int nframes, const uint8_t 
     S.meta[2 * m + 1] = -1;
   }
   EHIP(hipMemsetAsync(P.err, 0, sizeof(unsigned), st));
+  if (nmeas) EHIP(hipMemsetAsync(S.sse, 0, (size_t)njobs * 3 * sizeof(unsigned long long), st));
   TsArgs A;
   memset(&A, 0, sizeof(A));
   A.jobs = S.jobs;
@@ -859,14 +893,37 @@ int thor_enc_seq_end(thor_enc_t *e0, long long *stats) {
     fprintf(stderr, "thor_amd enc: sequence launch: device error flags 0x%x\n", err);
     return (err & 4) && !(err & 3) ? THOR_ERR_NOMEM : THOR_ERR_HIP;
   }
-  // each context's last frame is its chunk for thor_enc_frame_bytes
+  // the measured frames' sums (the launch is over: its atomics are complete)
+  int nmeas = 0;
+  for (int i = 0; i < R.n; i++) nmeas += R.measure[i] != 0;
+  if (nmeas) {
+    R.sse.resize((size_t)R.n * R.nframes * 3);
+    EHIP(hipMemcpy(R.sse.data(), S.sse, R.sse.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  }
+  // each context's last frame is its chunk for thor_enc_frame_bytes (and its sums thor_enc_frame_sse's)
   for (int i = 0; i < R.n; i++) {
     thor_enc *e = R.es[i];
     if (!e) continue;
+    e->sse_valid = R.measure[i] != 0;
+    for (int c = 0; c < 3; c++)
+      e->sse[c] = e->sse_valid ? (uint64_t)R.sse[((size_t)i * R.nframes + R.nframes - 1) * 3 + c] : 0;
     const long long sz = thor_enc_seq_chunk(e0, i, R.nframes - 1, nullptr, 0);
     e->chunk.resize((size_t)sz);
     thor_enc_seq_chunk(e0, i, R.nframes - 1, e->chunk.data(), e->chunk.size());
   }
+  return THOR_OK;
+}
+
+// Frame f of context i of the last ended launch: its Y, U, V sums of squared errors (the context was
+// measuring, thor_enc_measure_sse, when the launch began).
+int thor_enc_seq_sse(thor_enc_t *e0, int i, int f, uint64_t sse[3]) {
+  if (!e0 || !sse) return THOR_ERR_ARG;
+  EncPool &P = pool_for(e0->device);
+  std::lock_guard<std::mutex> pool_lock(P.mu);
+  TsPool &S = ts_pool_for(e0->device);
+  const TsRun &R = S.run;
+  if (R.active || i < 0 || i >= R.n || f < 0 || f >= R.nframes || !R.measure[i] || R.sse.empty()) return THOR_ERR_ARG;
+  for (int c = 0; c < 3; c++) sse[c] = (uint64_t)R.sse[((size_t)i * R.nframes + f) * 3 + c];
   return THOR_OK;
 }
 

@@ -109,12 +109,14 @@ class GpuDecoder:
         if not self.h:
             raise L.create_error("thor_dec_create")
         self._bufs = []
+        self._sse_out = None  # device words of sse() (24 bytes, on first use)
         self.use_slow_list = True  # False: every k_recon unit in planned order (same output; tests compare both)
 
     def close(self):
         for b in self._bufs:
             b.free()
         self._bufs = []
+        self._sse_out = None
         if self.h:
             self.lib.thor_dec_destroy(self.h)
             self.h = None
@@ -289,6 +291,19 @@ class GpuDecoder:
         L.check(self.lib.thor_dec_read_frame(self.h, frame_num, y.ctypes.data, u.ctypes.data, v.ctypes.data),
                 "thor_dec_read_frame")
         return y, u, v
+
+    def sse(self, frame_num: int, planes: L.ThorYuvPlanes):
+        """(Y, U, V) sums of squared errors of the resident frame `frame_num`
+        against `planes` (DEVICE pointers), computed on the device
+        (thor_dec_frame_sse on the context's stream; waits for it).  A frame that
+        is not resident raises with status THOR_ERR_REF."""
+        if self._sse_out is None:
+            self._sse_out = self.scratch(24)
+        out = self._sse_out
+        L.check(self.lib.thor_dec_frame_sse(self.h, frame_num, C.byref(planes), out), "thor_dec_frame_sse")
+        res = np.empty(3, np.uint64)
+        self.d2h(res, out)
+        return tuple(int(v) for v in res)
 
     def read_i420(self, frame_num: int) -> bytes:
         return b"".join(p.tobytes() for p in self.read(frame_num))

@@ -135,8 +135,59 @@ class GpuEncoder:
             raise RuntimeError("thor_enc_sb_costs: %d" % got)
         return out.reshape(-1, per.value)
 
+    def measure_quality(self, on: bool = True):
+        """thor_enc_measure_sse: every frame coded from now on is measured on the
+        device against its input (sse() / psnr()); not with a batch in flight."""
+        L.check(self.lib.thor_enc_measure_sse(self.h, 1 if on else 0), "thor_enc_measure_sse")
+
+    def sse(self):
+        """The last ended frame's sums of squared errors: (Y, U, V) ints."""
+        out = (C.c_uint64 * 3)()
+        L.check(self.lib.thor_enc_frame_sse(self.h, out), "thor_enc_frame_sse")
+        return tuple(int(v) for v in out)
+
+    def psnr(self):
+        """The last ended frame's (Y, U, V) PSNR in dB, as the reference prints it (thor_psnr)."""
+        return psnr_i420(self.sse(), self.W, self.H)
+
     def encode_all(self) -> bytes:
         return b"".join(self.encode_next() for _ in range(self.num_frames()))
+
+
+def psnr_i420(sse, width: int, height: int):
+    """(Y, U, V) PSNR of an I420 frame's three sums through thor_psnr (common/snr.c:60-61)."""
+    lib = L.load()
+    dims = ((width, height), (width >> 1, height >> 1), (width >> 1, height >> 1))
+    return tuple(float(lib.thor_psnr(int(s), w, h)) for s, (w, h) in zip(sse, dims))
+
+
+def yuv_planes(ptr: int, width: int, height: int, stride: int = 0) -> L.ThorYuvPlanes:
+    """thor_yuv_planes_t of a planar I420 frame at DEVICE address `ptr` (luma
+    stride `stride`, default width; chroma stride half of it, as thor_enc_frames reads its input)."""
+    s = stride or width
+    u = ptr + s * height
+    return L.ThorYuvPlanes(ptr, u, u + (s // 2) * (height // 2), s, s // 2)
+
+
+def sse_i420(a, b, width: int, height: int) -> np.ndarray:
+    """thor_sse_i420 of the plane-set pairs (a[i], b[i]) (ThorYuvPlanes of DEVICE
+    pointers): uint64 array (n, 3) of the Y, U, V sums of squared errors
+    (enqueued on the null stream and waited for)."""
+    lib = L.load()
+    n = len(a)
+    if n != len(b) or n == 0:
+        raise ValueError("sse_i420: two non-empty lists of the same length")
+    out = lib.thor_dev_alloc(24 * n)
+    if not out:
+        raise MemoryError("thor_dev_alloc")
+    try:
+        L.check(lib.thor_sse_i420((L.ThorYuvPlanes * n)(*a), (L.ThorYuvPlanes * n)(*b), n, width, height, out, None),
+                "thor_sse_i420")
+        res = np.empty((n, 3), np.uint64)
+        L.check(lib.thor_d2h(res.ctypes.data, out, res.nbytes), "thor_d2h")
+    finally:
+        lib.thor_dev_free(out)
+    return res
 
 
 def encode_batch(encs):
@@ -220,6 +271,13 @@ class SeqLaunch:
         buf = C.create_string_buffer(n)
         self.lib.thor_enc_seq_chunk(self.encs[0].h, i, f, buf, n)
         return buf.raw
+
+    def sse(self, i: int, f: int):
+        """(Y, U, V) sums of squared errors of frame f of encoder i (after end();
+        the encoder was measuring, measure_quality, when the launch began)."""
+        out = (C.c_uint64 * 3)()
+        L.check(self.lib.thor_enc_seq_sse(self.encs[0].h, i, f, out), "thor_enc_seq_sse")
+        return tuple(int(v) for v in out)
 
     def end(self):
         st = (C.c_longlong * 4)()

@@ -74,6 +74,7 @@ BATCHED_SYMBOLS = [
     "thor_ti_create", "thor_ti_destroy", "thor_interpolate_frames", "thor_ti_read_fields", "thor_ti_status",
     "thor_dev_alloc", "thor_dev_free", "thor_h2d", "thor_d2h", "thor_device_count", "thor_version",
     "thor_last_create_error",
+    "thor_sse_i420", "thor_psnr", "thor_dec_frame_sse", "thor_enc_measure_sse", "thor_enc_frame_sse", "thor_enc_seq_sse",
 ]
 L2_SURFACE_SYMBOLS = ["deblock_frame_y", "deblock_frame_uv", "make_top_and_left", "get_intra_prediction", "dequantize",
                       "reconstruct_block", "quantize"]
@@ -240,6 +241,19 @@ def load(path: str = LIB_PATH):
     L.thor_ti_read_fields.restype = i
     L.thor_ti_status.argtypes = [P]
     L.thor_ti_status.restype = i
+    # frame quality (sum of squared errors / PSNR on the device)
+    L.thor_sse_i420.argtypes = [C.POINTER(ThorYuvPlanes), C.POINTER(ThorYuvPlanes), i, i, i, P, P]
+    L.thor_sse_i420.restype = i
+    L.thor_psnr.argtypes = [C.c_uint64, i, i]
+    L.thor_psnr.restype = C.c_double
+    L.thor_dec_frame_sse.argtypes = [P, i, C.POINTER(ThorYuvPlanes), P]
+    L.thor_dec_frame_sse.restype = i
+    L.thor_enc_measure_sse.argtypes = [P, i]
+    L.thor_enc_measure_sse.restype = i
+    L.thor_enc_frame_sse.argtypes = [P, C.POINTER(C.c_uint64)]
+    L.thor_enc_frame_sse.restype = i
+    L.thor_enc_seq_sse.argtypes = [P, i, i, C.POINTER(C.c_uint64)]
+    L.thor_enc_seq_sse.restype = i
     # the reference's SIMD kernel surface (include/thor_kernels.h)
     u8p = P
     L.transform_simd.argtypes = [P, P, i, i]

@@ -5,7 +5,12 @@
 // be checked bit for bit against the reference encoder's .bit on a CPU-only
 // box.  Frame loop filters come from the CPU oracle (oracle/thor_oracle.c).
 //
-//   enc_host -if in.yuv -of out.bit [-rf rec.yuv] [-rdlog costs.bin] -width W -height H -n N [-qp ..] ...
+//   enc_host -if in.yuv -of out.bit [-rf rec.yuv] [-rdlog costs.bin] [-sselog sse.bin] -width W -height H -n N [-qp ..] ...
+//
+// -sselog: each coded frame's Y, U, V sums of squared errors -- the input frame
+// against the final reconstruction (snr_yuv's sums, common/snr.c:32-89) -- in
+// coding order as three little-endian uint64: what thor_enc_frame_sse reports
+// on the device, here with plain loops (tests/golden/quality.json).
 //
 // -rdlog: every superblock's top-level process_block costs (te_encode_sb's
 // cost record: delta-QP trials, then the final encode) as int32 records
@@ -41,7 +46,7 @@ struct HostFrame {
 int main(int argc, char **argv) {
   thor_enc_params_t P;
   te_default_params(&P);
-  const char *in = nullptr, *out = nullptr, *recf = nullptr, *rdlog = nullptr;
+  const char *in = nullptr, *out = nullptr, *recf = nullptr, *rdlog = nullptr, *sselog = nullptr;
   const char *trace_out = nullptr;
   (void)trace_out;
   int verbose = 0;
@@ -50,6 +55,7 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[i], "-of")) out = argv[i + 1];
     else if (!strcmp(argv[i], "-rf")) recf = argv[i + 1];
     else if (!strcmp(argv[i], "-rdlog")) rdlog = argv[i + 1];
+    else if (!strcmp(argv[i], "-sselog")) sselog = argv[i + 1];
     else if (!strcmp(argv[i], "-v")) verbose = atoi(argv[i + 1]);
 #if defined(THOR_ENC_TRACE)
     else if (!strcmp(argv[i], "-trace_frame")) te_trace_frame = atoi(argv[i + 1]);
@@ -73,7 +79,8 @@ int main(int argc, char **argv) {
 #endif
   FILE *fi = fopen(in, "rb"), *fo = fopen(out, "wb"), *fr = recf ? fopen(recf, "wb") : nullptr;
   FILE *frd = rdlog ? fopen(rdlog, "wb") : nullptr;
-  if (!fi || !fo || (rdlog && !frd)) return 3;
+  FILE *fss = sselog ? fopen(sselog, "wb") : nullptr;
+  if (!fi || !fo || (rdlog && !frd) || (sselog && !fss)) return 3;
   const int ntrial = P.max_delta_qp ? (2 * P.max_delta_qp) / (P.delta_qp_step > 0 ? P.delta_qp_step : 1) + 1 : 0;
   std::vector<int32_t> costs(ntrial + 1);
   const size_t fsz = (size_t)W * H * 3 / 2;
@@ -198,6 +205,22 @@ int main(int argc, char **argv) {
     fwrite(hdr, 1, 4, fo);
     fwrite(fb.bytes.data(), 1, nb, fo);
     if (verbose) fprintf(stderr, "frame %d type %d qp %d bytes %u\n", pl.frame_num, pl.frame_type, pl.qp, nb);
+    if (fss) {  // the frame is final (deblocked, CLPF'd): its squared errors against the input
+      auto plane = [](const uint8_t *a, int as, const uint8_t *b, int bs, int w, int h) {
+        uint64_t s = 0;
+        for (int i = 0; i < h; i++)
+          for (int j = 0; j < w; j++) {
+            const int d = (int)a[i * as + j] - (int)b[i * bs + j];
+            s += (uint64_t)(d * d);
+          }
+        return s;
+      };
+      const uint64_t sse[3] = {plane(F.oy, F.osy, cur.f.y, cur.f.stride_y, W, H),
+                               plane(F.ou, F.osc, cur.f.u, cur.f.stride_c, W / 2, H / 2),
+                               plane(F.ov, F.osc, cur.f.v, cur.f.stride_c, W / 2, H / 2)};
+      for (int c = 0; c < 3; c++)
+        for (int b = 0; b < 8; b++) fputc((int)((sse[c] >> (8 * b)) & 255), fss);
+    }
     if (fr) {  // coding order == display order for the low-delay configurations this harness checks
       for (int i = 0; i < H; i++) fwrite(cur.f.y + i * cur.f.stride_y, 1, W, fr);
       for (int i = 0; i < H / 2; i++) fwrite(cur.f.u + i * cur.f.stride_c, 1, W / 2, fr);
@@ -223,6 +246,7 @@ int main(int argc, char **argv) {
   fclose(fo);
   if (fr) fclose(fr);
   if (frd) fclose(frd);
+  if (fss) fclose(fss);
   free(SM);
   return 0;
 }

@@ -4,7 +4,10 @@
 .bit, report per-frame wall times.  --extra appends encoder flags to the
 clip's (one string, e.g. --extra="-rdoq 1"); the bits are then checked, outside the timed
 region as always, against --bit-md5 (rdoq.json's speed_4k for k4_low with
--rdoq 1: tools/make_rdoq_goldens.py) or, with no md5 given, not at all."""
+-rdoq 1: tools/make_rdoq_goldens.py) or, with no md5 given, not at all.
+--quality turns the on-device frame quality measurement on for every context
+(thor_enc_measure_sse: one more launch per batch) and prints the
+last frame's PSNR of the first stream."""
 import argparse
 import hashlib
 import json
@@ -29,6 +32,7 @@ def main():
                     help="code only the first LIMIT coded frames of the plan (the GOP as for --frames)")
     ap.add_argument("--extra", default="", help="encoder flags appended to the clip's own, as one string")
     ap.add_argument("--bit-md5", default="", help="md5 of the whole reference .bit for the clip with --extra")
+    ap.add_argument("--quality", action="store_true", help="measure every coded frame's SSE on the device")
     a = ap.parse_args()
     a.extra = shlex.split(a.extra)
     meta = json.load(open(os.path.join(ROOT, "tests", "golden", "streams.json")))[a.name]
@@ -41,6 +45,8 @@ def main():
         encs = [GpuEncoder(params_for(meta["config"], w, h, n, list(meta["extra"]) + a.extra)) for _ in range(B)]
         for e in encs:
             e.upload_sequence(frames)
+            if a.quality:
+                e.measure_quality()
         out = [b""] * B
         t_frames = []
         for i in range(a.limit or n):
@@ -59,6 +65,8 @@ def main():
         tot = sum(t_frames)
         res[B] = dict(ok=ok, total_s=tot, frame_ms=[round(1000 * t, 2) for t in t_frames],
                       mpx_s=B * w * h * (a.limit or n) / tot / 1e6)
+        if a.quality:
+            res[B]["last_psnr"] = [round(v, 4) for v in encs[0].psnr()]
         print(a.name, "batch", B, json.dumps(res[B]), flush=True)
         for e in encs:
             e.close()
