@@ -624,6 +624,58 @@ int thor_enc_frame_sse(const thor_enc_t *e, uint64_t sse[3]);
  * THOR_ERR_ARG when that context was not measuring. */
 int thor_enc_seq_sse(thor_enc_t *e0, int i, int f, uint64_t sse[3]);
 
+/* ---- colour conversion: I420 <-> RGB on the device ------------------------ *
+ * RGB images in HBM in and out of the codec (k_csc_to_rgb / k_csc_from_rgb,
+ * thor_amd/csrc/color.hip).  The arithmetic is specified in integers (DESIGN.md
+ * sec. 7c) and is bit-exact on every run and every launch shape: 14-bit fixed
+ * point 3x3 tables per matrix / range, one rounding per sample; chroma is
+ * box-filtered (2x2 sum, one rounding) towards I420 and taken nearest or
+ * bilinear (centre-sited, 9-3-3-1, edges clamped) towards RGB.  A float channel
+ * is byte * (float32 nearest 1/255) out, clamp(rint(v * 255)) in (NaN -> 0). */
+#define THOR_RGB8_PACKED 0   /* H x W x 3 bytes, R G B; stride = bytes per row (>= 3 W)            */
+#define THOR_RGB8_PLANAR 1   /* 3 x H x W bytes; stride = bytes per row, plane_stride between planes */
+#define THOR_RGBF32_PLANAR 2 /* 3 x H x W float32 in [0,1]; strides in bytes, multiples of 4; data 4-byte aligned */
+typedef struct thor_image {
+  void *data; /* DEVICE pointer to the first sample (R of pixel (0, 0)) */
+  int32_t format, stride;
+  int64_t plane_stride; /* bytes from a plane to the next (planar formats; ignored for packed) */
+} thor_image_t;
+typedef struct thor_csc {
+  int32_t matrix;     /* 0 BT.601, 1 BT.709 */
+  int32_t full_range; /* 0: Y 16..235, chroma 16..240; 1: 0..255 */
+  int32_t chroma_up;  /* 0 nearest, 1 bilinear; to-RGB only */
+} thor_csc_t;
+/* Most images one launch carries in its kernel arguments; a longer batch is
+ * split into several launches on the same stream. */
+#define THOR_CSC_LAUNCH_IMAGES 16
+
+/* Host, no device: the forward (Y, Cb, Cr from R, G, B) and inverse (R, G, B
+ * from Y - yo, Cb - 128, Cr - 128) tables, row-major 3x3, 14-bit fixed point.
+ * Either output may be NULL.  THOR_ERR_ARG for a matrix / range outside 0, 1. */
+int thor_csc_coeffs(int matrix, int full_range, int32_t fwd[9], int32_t inv[9]);
+/* n images in one batch: src / dst are HOST arrays of n descriptors holding
+ * DEVICE pointers, every image with its own strides and any alignment (aligned
+ * pointers and strides take the wide loads and stores); all images of a call
+ * share format, size and csc.  1 <= n <= 65535; width, height even and >= 2
+ * (any even size, not only the codec's multiples of 8).  Only the width x
+ * height samples are written: row padding and the bytes between planes are
+ * left alone.  THOR_ERR_ARG -- before any device call -- for NULL pointers, bad
+ * enums, odd sizes, strides below a row, a float stride or pointer that is no
+ * multiple of 4.  Enqueued on `stream`; returns without waiting. */
+int thor_i420_to_rgb(const thor_yuv_planes_t *src, const thor_image_t *dst, int n, int width, int height,
+                     const thor_csc_t *csc, void *stream);
+int thor_rgb_to_i420(const thor_image_t *src, const thor_yuv_planes_t *dst, int n, int width, int height,
+                     const thor_csc_t *csc, void *stream);
+/* The decoder's resident frame `frame_num`: its interior DEVICE planes and
+ * strides (inside the padded ring slot), valid until the ring evicts the
+ * slot; a reader orders itself after the context's stream.  THOR_ERR_REF when
+ * the frame is not resident. */
+int thor_dec_frame_planes(thor_dec_t *d, int frame_num, thor_yuv_planes_t *out);
+/* That frame converted into `dst` (DEVICE) by the same kernel, enqueued on the
+ * context's stream after the work already queued there (the frame's decode
+ * included); returns without waiting.  THOR_ERR_REF when not resident. */
+int thor_dec_frame_rgb(thor_dec_t *d, int frame_num, const thor_image_t *dst, const thor_csc_t *csc);
+
 /* ---- device memory helpers (so the C-ABI is usable without torch) ------ */
 void *thor_dev_alloc(size_t bytes);
 int thor_dev_free(void *p);

@@ -103,6 +103,7 @@ class GpuDecoder:
         if self.lib.thor_device_count() <= 0:
             raise RuntimeError("no HIP device visible: the GPU decode path has no CPU fallback")
         self.seq = seq
+        self.device = device
         cs = L.ThorSeq(seq.width, seq.height, seq.bipred, seq.deblocking, seq.clpf, seq.tb_split_enable,
                        getattr(seq, "interp_ref", 0))
         self.h = self.lib.thor_dec_create(C.byref(cs), device, slots)
@@ -304,6 +305,51 @@ class GpuDecoder:
         res = np.empty(3, np.uint64)
         self.d2h(res, out)
         return tuple(int(v) for v in res)
+
+    def planes(self, frame_num: int) -> L.ThorYuvPlanes:
+        """The resident frame's interior DEVICE planes and strides
+        (thor_dec_frame_planes), valid until the ring evicts the slot; a reader
+        orders itself after the context's stream.  A frame that is not resident
+        raises with status THOR_ERR_REF."""
+        out = L.ThorYuvPlanes()
+        L.check(self.lib.thor_dec_frame_planes(self.h, frame_num, C.byref(out)), "thor_dec_frame_planes")
+        return out
+
+    def read_rgb(self, frame_num: int, *, matrix="bt709", full_range=False, chroma="bilinear", layout="chw",
+                 dtype=None):
+        """The resident frame as an RGB torch tensor on the device: (3, H, W)
+        ("chw") or (H, W, 3) ("hwc"), uint8 (default) or float32 in [0, 1]
+        ("chw" only).  thor_dec_frame_rgb converts it on the decoder's stream,
+        after the frame's decode; torch's current stream waits for an event
+        recorded there, so torch work that follows sees the pixels -- no host
+        synchronisation.  A frame that is not resident raises with status
+        THOR_ERR_REF."""
+        import torch
+
+        from . import color
+
+        dtype = torch.uint8 if dtype is None else dtype
+        if layout not in ("hwc", "chw") or dtype not in (torch.uint8, torch.float32) or \
+                (dtype == torch.float32 and layout != "chw"):
+            raise ValueError("layout 'hwc' or 'chw'; dtype uint8 or float32 (float32 with 'chw' only)")
+        W, H = self.seq.width, self.seq.height
+        dev = torch.device("cuda", self.device)
+        c = color.csc(matrix, full_range, chroma)
+        with torch.cuda.device(dev):
+            out = torch.empty((1, H, W, 3) if layout == "hwc" else (1, 3, H, W), dtype=dtype, device=dev)
+            img = color.rgb_images(out, layout)[0]
+            dstream = torch.cuda.ExternalStream(self.stream() or 0, device=dev)
+            cur = torch.cuda.current_stream()
+            dstream.wait_stream(cur)  # (the allocator may hand out memory whose last use is queued on `cur`)
+            L.check(self.lib.thor_dec_frame_rgb(self.h, frame_num, img, C.byref(c)), "thor_dec_frame_rgb")
+            ev = torch.cuda.Event()
+            ev.record(dstream)
+            cur.wait_event(ev)
+            # No out.record_stream(dstream): the tensor's memory belongs to `cur`, which now waits for
+            # the conversion, so the allocator cannot hand it out early -- and a recorded use would make
+            # the allocator touch the decoder's stream when the tensor is freed, possibly after close()
+            # has destroyed that stream.
+        return out[0]
 
     def read_i420(self, frame_num: int) -> bytes:
         return b"".join(p.tobytes() for p in self.read(frame_num))

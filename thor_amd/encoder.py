@@ -82,6 +82,39 @@ class GpuEncoder:
             self.lib.thor_dev_free(self.seq_dev)
         self.seq_dev, self.own_seq, self.nin = ptr, False, nframes
 
+    def set_input_rgb(self, rgb, *, matrix="bt709", full_range=False, layout=None):
+        """Make the `n` RGB images of a CUDA tensor the input sequence (what
+        upload_sequence does from the host): uint8 (n, H, W, 3), uint8
+        (n, 3, H, W) or float32 (n, 3, H, W) in [0, 1], converted on the device
+        in one call (thor_rgb_to_i420 on torch's current stream) into an owned
+        I420 buffer.  torch's stream is synchronised once, so the conversion is
+        done before the encoder's work begins."""
+        import torch
+
+        from . import color
+
+        imgs, n, W, H, keep = color.rgb_images(rgb, layout)
+        if (W, H) != (self.W, self.H):
+            raise ValueError("RGB images are %dx%d, the encoder codes %dx%d" % (W, H, self.W, self.H))
+        seq = self.lib.thor_dev_alloc(n * self.fsize)
+        if not seq:
+            raise MemoryError("thor_dev_alloc")
+        try:
+            dst = (L.ThorYuvPlanes * n)(*[color.i420_planes(seq + i * self.fsize, W, H) for i in range(n)])
+            c = color.csc(matrix, full_range)
+            with torch.cuda.device(rgb.device):
+                cur = torch.cuda.current_stream()
+                L.check(self.lib.thor_rgb_to_i420(imgs, dst, n, W, H, C.byref(c), cur.cuda_stream),
+                        "thor_rgb_to_i420")
+                cur.synchronize()
+        except Exception:
+            self.lib.thor_dev_free(seq)
+            raise
+        del keep
+        if self.seq_dev and self.own_seq:
+            self.lib.thor_dev_free(self.seq_dev)
+        self.seq_dev, self.own_seq, self.nin = seq, True, n
+
     def reset(self):
         """Start the sequence again (thor_enc_reset): same input, same .bit."""
         L.check(self.lib.thor_enc_reset(self.h), "thor_enc_reset")

@@ -27,6 +27,20 @@ class ThorYuvPlanes(C.Structure):
                 ("stride_c", C.c_int32)]
 
 
+class ThorImage(C.Structure):
+    """thor_image_t (include/thor_amd.h): an RGB image in device memory."""
+    _fields_ = [("data", C.c_void_p), ("format", C.c_int32), ("stride", C.c_int32), ("plane_stride", C.c_int64)]
+
+
+class ThorCsc(C.Structure):
+    """thor_csc_t (include/thor_amd.h)."""
+    _fields_ = [("matrix", C.c_int32), ("full_range", C.c_int32), ("chroma_up", C.c_int32)]
+
+
+THOR_RGB8_PACKED, THOR_RGB8_PLANAR, THOR_RGBF32_PLANAR = 0, 1, 2
+THOR_CSC_LAUNCH_IMAGES = 16
+
+
 class ThorEncParams(C.Structure):
     """thor_enc_params_t (include/thor_amd.h) = enc_params (enc/mainenc.h:34-88)."""
     _fields_ = [(n, C.c_int32) for n in ("width", "height", "qp", "num_frames", "skip")] + \
@@ -75,6 +89,7 @@ BATCHED_SYMBOLS = [
     "thor_dev_alloc", "thor_dev_free", "thor_h2d", "thor_d2h", "thor_device_count", "thor_version",
     "thor_last_create_error",
     "thor_sse_i420", "thor_psnr", "thor_dec_frame_sse", "thor_enc_measure_sse", "thor_enc_frame_sse", "thor_enc_seq_sse",
+    "thor_csc_coeffs", "thor_i420_to_rgb", "thor_rgb_to_i420", "thor_dec_frame_planes", "thor_dec_frame_rgb",
 ]
 L2_SURFACE_SYMBOLS = ["deblock_frame_y", "deblock_frame_uv", "make_top_and_left", "get_intra_prediction", "dequantize",
                       "reconstruct_block", "quantize"]
@@ -254,6 +269,17 @@ def load(path: str = LIB_PATH):
     L.thor_enc_frame_sse.restype = i
     L.thor_enc_seq_sse.argtypes = [P, i, i, C.POINTER(C.c_uint64)]
     L.thor_enc_seq_sse.restype = i
+    # colour conversion (I420 <-> RGB images on the device)
+    L.thor_csc_coeffs.argtypes = [i, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.thor_csc_coeffs.restype = i
+    L.thor_i420_to_rgb.argtypes = [C.POINTER(ThorYuvPlanes), C.POINTER(ThorImage), i, i, i, C.POINTER(ThorCsc), P]
+    L.thor_i420_to_rgb.restype = i
+    L.thor_rgb_to_i420.argtypes = [C.POINTER(ThorImage), C.POINTER(ThorYuvPlanes), i, i, i, C.POINTER(ThorCsc), P]
+    L.thor_rgb_to_i420.restype = i
+    L.thor_dec_frame_planes.argtypes = [P, i, C.POINTER(ThorYuvPlanes)]
+    L.thor_dec_frame_planes.restype = i
+    L.thor_dec_frame_rgb.argtypes = [P, i, C.POINTER(ThorImage), C.POINTER(ThorCsc)]
+    L.thor_dec_frame_rgb.restype = i
     # the reference's SIMD kernel surface (include/thor_kernels.h)
     u8p = P
     L.transform_simd.argtypes = [P, P, i, i]
