@@ -676,6 +676,64 @@ int thor_dec_frame_planes(thor_dec_t *d, int frame_num, thor_yuv_planes_t *out);
  * included); returns without waiting.  THOR_ERR_REF when not resident. */
 int thor_dec_frame_rgb(thor_dec_t *d, int frame_num, const thor_image_t *dst, const thor_csc_t *csc);
 
+/* ---- frame scaling: bit-exact I420 resize on the device ------------------- *
+ * One source coded at several sizes (an encode ladder), thumbnails of a decoded
+ * frame: planar I420 frames in HBM resized by k_scale_i420
+ * (thor_amd/csrc/scale.hip).  The arithmetic is specified in integers
+ * (DESIGN.md sec. 7d), so the scaled bytes are a function of the source bytes:
+ * the same on every run and every launch shape.
+ *
+ * One axis, S source and D destination samples, centre-sited for luma and
+ * chroma alike; M = 2 max(S, D) (the kernel is stretched by S / D when
+ * shrinking).  Output d sits at c2 = (2d + 1) S - D (in units of 1 / 2D); its
+ * taps are the integers s with u = |2 D s - c2| < R M (R = 1 triangle, R = 2
+ * Catmull-Rom, a = -1/2), a tap outside [0, S - 1] reading the edge sample.
+ * Weight numerators: triangle M - u; cubic 3u^3 - 5M u^2 + 2M^3 (u < M),
+ * -u^3 + 5M u^2 - 8M^2 u + 4M^3 (M <= u < 2M).  With T their sum,
+ * c_k = floor((2 P_k 16384 + T) / 2T), and 16384 - sum c_k goes to the first tap
+ * with the largest P: every row sums to 16384, and S == D is the identity.
+ * Two passes, horizontal first:
+ *   h   = (sum ch_k src[y][x_k] + 128) >> 8                 (int16, 6 fractional bits)
+ *   out = clamp((sum cv_k h[y_k][d] + 2^19) >> 20, 0, 255)
+ * Y goes from (sw, sh) to (dw, dh), U and V between the halved sizes. */
+#define THOR_SCALE_BILINEAR 0
+#define THOR_SCALE_BICUBIC 1
+#define THOR_SCALE_MAX_TAPS 33  /* taps per axis: 2R max(1, ceil(S / D)) + 1 at most */
+#define THOR_SCALE_MAX_SIZE 8192
+/* Most images one launch carries in its kernel arguments; a longer batch is
+ * split into several launches on the same stream. */
+#define THOR_SCALE_LAUNCH_IMAGES 16
+typedef struct thor_scaler thor_scaler_t;
+
+/* Host, no device: the table of one axis.  first[d] = the first tap of output d
+ * (not clamped: negative at the left edge), coef[d * ntaps + k] the coefficient
+ * of tap first[d] + k, rows zero-padded to *ntaps = the axis maximum.  With
+ * first or coef NULL only *ntaps is written.  1 <= S, D <= 8192, S <= 8 D. */
+int thor_scale_taps(int S, int D, int filter, int32_t *first, int16_t *coef, int *ntaps);
+/* Host, no device: THOR_OK when a scaler of these sizes can be created: all
+ * four even, 2 .. 8192, sw <= 8 dw, sh <= 8 dh (enlarging is not restricted),
+ * filter one of the two.  THOR_ERR_ARG otherwise. */
+int thor_scale_check(int sw, int sh, int dw, int dh, int filter);
+/* A scaler of one size pair and filter: builds the four axis tables (luma and
+ * chroma, horizontal and vertical; the edge clamp folded into the coefficients)
+ * and uploads them once, so a scaling call allocates, uploads and looks up
+ * nothing.  NULL on failure (thor_last_create_error). */
+thor_scaler_t *thor_scaler_create(int sw, int sh, int dw, int dh, int filter, int device);
+void thor_scaler_destroy(thor_scaler_t *s);
+/* n frames in one batch: src / dst are HOST arrays of n descriptors holding
+ * DEVICE pointers, every frame with its own strides and any alignment.
+ * 1 <= n <= 65535.  Only the dw x dh (chroma: halved) samples are written: row
+ * padding and the bytes around the planes are left alone.  THOR_ERR_ARG --
+ * before any device call -- for NULL pointers, strides below a row, n out of
+ * range.  Enqueued on `stream`; returns without waiting. */
+int thor_scale_i420(thor_scaler_t *s, const thor_yuv_planes_t *src, const thor_yuv_planes_t *dst, int n, void *stream);
+/* The decoder's resident frame `frame_num` scaled into `dst` (DEVICE) by the
+ * same kernel, enqueued on the context's stream after the work already queued
+ * there (the frame's decode included); returns without waiting.  THOR_ERR_ARG
+ * when the scaler's source size (or device) is not the stream's, THOR_ERR_REF
+ * when the frame is not resident. */
+int thor_dec_frame_scaled(thor_dec_t *d, int frame_num, thor_scaler_t *s, const thor_yuv_planes_t *dst);
+
 /* ---- device memory helpers (so the C-ABI is usable without torch) ------ */
 void *thor_dev_alloc(size_t bytes);
 int thor_dev_free(void *p);

@@ -111,6 +111,7 @@ class GpuDecoder:
             raise L.create_error("thor_dec_create")
         self._bufs = []
         self._sse_out = None  # device words of sse() (24 bytes, on first use)
+        self._scalers = {}  # read_scaled: (dw, dh, filter) -> (Scaler, device buffer of one scaled frame)
         self.use_slow_list = True  # False: every k_recon unit in planned order (same output; tests compare both)
 
     def close(self):
@@ -118,6 +119,9 @@ class GpuDecoder:
             b.free()
         self._bufs = []
         self._sse_out = None
+        for sc, _ in self._scalers.values():
+            sc.close()
+        self._scalers = {}
         if self.h:
             self.lib.thor_dec_destroy(self.h)
             self.h = None
@@ -350,6 +354,25 @@ class GpuDecoder:
             # the allocator touch the decoder's stream when the tensor is freed, possibly after close()
             # has destroyed that stream.
         return out[0]
+
+    def read_scaled(self, frame_num: int, dw: int, dh: int, filter="bicubic") -> bytes:
+        """The resident frame scaled to dw x dh on the device (thor_dec_frame_scaled
+        on the context's stream, after the frame's decode), as I420 bytes: a
+        thumbnail or preview costs a copy of the small frame only.  One Scaler and
+        one device frame per (size, filter) are kept on the decoder until
+        close().  A frame that is not resident raises with status THOR_ERR_REF."""
+        from . import scale
+
+        key = (dw, dh, scale.filter_id(filter))
+        if key not in self._scalers:
+            sc = scale.Scaler(self.seq.width, self.seq.height, dw, dh, key[2], self.device)
+            self._scalers[key] = (sc, self.scratch(dw * dh * 3 // 2))
+        sc, buf = self._scalers[key]
+        dst = scale.i420_planes(buf, dw, dh)
+        L.check(self.lib.thor_dec_frame_scaled(self.h, frame_num, sc.h, C.byref(dst)), "thor_dec_frame_scaled")
+        out = np.empty(dw * dh * 3 // 2, np.uint8)
+        self.d2h(out, buf)
+        return out.tobytes()
 
     def read_i420(self, frame_num: int) -> bytes:
         return b"".join(p.tobytes() for p in self.read(frame_num))

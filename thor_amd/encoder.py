@@ -42,6 +42,7 @@ class GpuEncoder:
         self.p = params
         if self.lib.thor_enc_check_params(C.byref(params)) != 0:
             raise ValueError("encoder parameters not supported")
+        self.device = device
         self.h = self.lib.thor_enc_create(C.byref(params), device)
         if not self.h:
             raise L.create_error("thor_enc_create")
@@ -50,11 +51,15 @@ class GpuEncoder:
         self.seq_dev = None
         self.own_seq = False
         self.nin = 0
+        self._scalers = {}  # set_input_scaled: (width, height, filter) -> Scaler
 
     def close(self):
         if self.h:
             self.lib.thor_enc_destroy(self.h)
             self.h = None
+        for sc in getattr(self, "_scalers", {}).values():
+            sc.close()
+        self._scalers = {}
         if self.seq_dev and self.own_seq:
             self.lib.thor_dev_free(self.seq_dev)
         self.seq_dev = None
@@ -114,6 +119,32 @@ class GpuEncoder:
         if self.seq_dev and self.own_seq:
             self.lib.thor_dev_free(self.seq_dev)
         self.seq_dev, self.own_seq, self.nin = seq, True, n
+
+    def set_input_scaled(self, ptr: int, nframes: int, width: int, height: int, filter="bicubic"):
+        """Make `nframes` contiguous I420 frames of another size at DEVICE
+        address `ptr` (frame k at ptr + k * width*height*3/2) the input
+        sequence, scaled to the encoder's size on the device in one call
+        (thor_scale_i420 on the encoder's stream, so the encoder's own launches
+        and every batch it joins come after it) into an owned buffer: one rung of
+        an encode ladder.  The scaled bytes are a function of the source bytes
+        (DESIGN.md sec. 7d).  No torch involved; the source must stay valid until
+        the first frame has been coded."""
+        from . import scale
+
+        key = (width, height, scale.filter_id(filter))
+        if key not in self._scalers:  # kept until close(): its tables must outlive the launch
+            self._scalers[key] = scale.Scaler(width, height, self.W, self.H, key[2], self.device)
+        seq = self.lib.thor_dev_alloc(nframes * self.fsize)
+        if not seq:
+            raise MemoryError("thor_dev_alloc")
+        try:
+            self._scalers[key].run_frames(ptr, seq, nframes, self.stream())
+        except Exception:
+            self.lib.thor_dev_free(seq)
+            raise
+        if self.seq_dev and self.own_seq:
+            self.lib.thor_dev_free(self.seq_dev)
+        self.seq_dev, self.own_seq, self.nin = seq, True, nframes
 
     def reset(self):
         """Start the sequence again (thor_enc_reset): same input, same .bit."""

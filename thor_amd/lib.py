@@ -39,6 +39,8 @@ class ThorCsc(C.Structure):
 
 THOR_RGB8_PACKED, THOR_RGB8_PLANAR, THOR_RGBF32_PLANAR = 0, 1, 2
 THOR_CSC_LAUNCH_IMAGES = 16
+THOR_SCALE_BILINEAR, THOR_SCALE_BICUBIC = 0, 1
+THOR_SCALE_MAX_TAPS, THOR_SCALE_MAX_SIZE, THOR_SCALE_LAUNCH_IMAGES = 33, 8192, 16
 
 
 class ThorEncParams(C.Structure):
@@ -90,6 +92,8 @@ BATCHED_SYMBOLS = [
     "thor_last_create_error",
     "thor_sse_i420", "thor_psnr", "thor_dec_frame_sse", "thor_enc_measure_sse", "thor_enc_frame_sse", "thor_enc_seq_sse",
     "thor_csc_coeffs", "thor_i420_to_rgb", "thor_rgb_to_i420", "thor_dec_frame_planes", "thor_dec_frame_rgb",
+    "thor_scale_taps", "thor_scale_check", "thor_scaler_create", "thor_scaler_destroy", "thor_scale_i420",
+    "thor_dec_frame_scaled",
 ]
 L2_SURFACE_SYMBOLS = ["deblock_frame_y", "deblock_frame_uv", "make_top_and_left", "get_intra_prediction", "dequantize",
                       "reconstruct_block", "quantize"]
@@ -280,6 +284,18 @@ def load(path: str = LIB_PATH):
     L.thor_dec_frame_planes.restype = i
     L.thor_dec_frame_rgb.argtypes = [P, i, C.POINTER(ThorImage), C.POINTER(ThorCsc)]
     L.thor_dec_frame_rgb.restype = i
+    # frame scaling (bit-exact I420 resize on the device)
+    L.thor_scale_taps.argtypes = [i, i, i, C.POINTER(C.c_int32), C.POINTER(C.c_int16), C.POINTER(C.c_int)]
+    L.thor_scale_taps.restype = i
+    L.thor_scale_check.argtypes = [i, i, i, i, i]
+    L.thor_scale_check.restype = i
+    L.thor_scaler_create.argtypes = [i, i, i, i, i, i]
+    L.thor_scaler_create.restype = P
+    L.thor_scaler_destroy.argtypes = [P]
+    L.thor_scale_i420.argtypes = [P, C.POINTER(ThorYuvPlanes), C.POINTER(ThorYuvPlanes), i, P]
+    L.thor_scale_i420.restype = i
+    L.thor_dec_frame_scaled.argtypes = [P, i, P, C.POINTER(ThorYuvPlanes)]
+    L.thor_dec_frame_scaled.restype = i
     # the reference's SIMD kernel surface (include/thor_kernels.h)
     u8p = P
     L.transform_simd.argtypes = [P, P, i, i]
