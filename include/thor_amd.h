@@ -624,6 +624,57 @@ int thor_enc_frame_sse(const thor_enc_t *e, uint64_t sse[3]);
  * THOR_ERR_ARG when that context was not measuring. */
 int thor_enc_seq_sse(thor_enc_t *e0, int i, int f, uint64_t sse[3]);
 
+/* ---- frame quality: SSIM on the device ------------------------------------ *
+ * The metric encode ladders are tuned with, in the x264 / ffmpeg `ssim` layout,
+ * computed where the frames live (k_ssim_i420, thor_amd/csrc/ssim.hip).  The
+ * reference has no SSIM: the arithmetic is specified in integers (DESIGN.md
+ * sec. 7e) and is bit-exact on every run and every launch shape.
+ *
+ * A plane of w x h pixels has (w>>2) x (h>>2) 4x4 blocks (the last w & 3
+ * columns and h & 3 rows are not read) and ((w>>2) - 1) x ((h>>2) - 1) windows
+ * of 2x2 blocks.  With s1 = sum a, s2 = sum b, ss = sum a^2 + sum b^2,
+ * s12 = sum a b over a window's 64 pixels, C1 = 416, C2 = 235963:
+ *   vars = 64 ss - s1^2 - s2^2            covar = 64 s12 - s1 s2
+ *   A1 = 2 s1 s2 + C1   B1 = s1^2 + s2^2 + C1   A2 = 2 covar + C2   B2 = vars + C2
+ *   q = rint(((double)A1 * (double)A2) / ((double)B1 * (double)B2) * 2^30)
+ * (IEEE double, round to nearest even; |q| <= 2^30, q = THOR_SSIM_ONE for
+ * a == b, negative where the covariance is).  A plane's result is the int64
+ * sum of q over its windows: an exact integer, whatever the order of summation. */
+#define THOR_SSIM_ONE (1 << 30)
+/* Windows of one width x height plane; 0 when either is below 8. */
+int thor_ssim_windows(int width, int height);
+/* sums[3*i + {0,1,2}] = sum of q over the Y (width x height), U, V
+ * ((width>>1) x (height>>1)) planes of frame pair i.  a / b: HOST arrays of n
+ * plane sets (DEVICE pointers, own strides, any alignment; 16-byte aligned
+ * pointers and strides take 16-byte loads); sums: DEVICE, 3*n int64,
+ * overwritten.  width, height >= 16 (chroma has a window), 1 <= n <= 65535,
+ * else THOR_ERR_ARG before any device call.  Enqueued on `stream`; returns
+ * without waiting. */
+int thor_ssim_i420(const thor_yuv_planes_t *a, const thor_yuv_planes_t *b, int n, int width, int height,
+                   int64_t *sums, void *stream);
+/* sum / (2^30 * windows) of a width x height plane (for a chroma plane pass
+ * its size, (width>>1, height>>1)); NaN for a plane without a window. */
+double thor_ssim(int64_t sum, int width, int height);
+/* -10 * log10(1 - ssim); +inf at 1. */
+double thor_ssim_db(double ssim);
+/* The decoder's resident frame `frame_num` against `orig` (DEVICE planes, own
+ * strides): the three sums into sums_dev (DEVICE, 3 int64, overwritten),
+ * enqueued on the context's stream after the work already queued there (the
+ * frame's decode included); returns without waiting.  THOR_ERR_REF when the
+ * frame is not resident. */
+int thor_dec_frame_ssim(thor_dec_t *d, int frame_num, const thor_yuv_planes_t *orig, int64_t *sums_dev);
+/* The last ended frame's final reconstruction (the one thor_enc_read_recon
+ * copies out) against `orig` (DEVICE planes, own strides): the three sums into
+ * sums_dev (DEVICE, 3 int64, overwritten), enqueued on the encoder's stream;
+ * returns without waiting.  The reconstruction is final there: the frame has
+ * ended, the padding kernel writes only outside the interior, and nothing of
+ * the next frame has started.  THOR_ERR_ARG when no frame has ended, and with a
+ * batch or a sequence launch in flight on the context (thor_enc_measure_sse's
+ * condition).  Nothing is added to the encoder's own launches: frames inside a
+ * thor_enc_frames batch other than the last, and the reconstructions a sequence
+ * launch overwrites, are not measurable this way. */
+int thor_enc_recon_ssim(thor_enc_t *e, const thor_yuv_planes_t *orig, int64_t *sums_dev);
+
 /* ---- colour conversion: I420 <-> RGB on the device ------------------------ *
  * RGB images in HBM in and out of the codec (k_csc_to_rgb / k_csc_from_rgb,
  * thor_amd/csrc/color.hip).  The arithmetic is specified in integers (DESIGN.md

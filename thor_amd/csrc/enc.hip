@@ -1620,6 +1620,26 @@ int thor_enc_read_recon(thor_enc_t *e, uint8_t *y, uint8_t *u, uint8_t *v) {
   return THOR_OK;
 }
 
+// SSIM of the last ended frame's reconstruction against `orig` (ssim.hip), enqueued on the context's
+// stream.  The reconstruction is final there: the frame has ended, so its last stage that writes the
+// interior (CLPF, or deblocking, or the RD loop) is done, k_enc_pad writes only outside the interior,
+// and nothing of the next frame has started -- hence not with a batch or a sequence launch in flight
+// on the context (thor_enc_measure_sse's condition).
+int thor_enc_recon_ssim(thor_enc_t *e, const thor_yuv_planes_t *orig, int64_t *sums_dev) {
+  if (!e || !orig || !sums_dev || e->last_slot < 0 || e->W < 16 || e->H < 16 || ts_member(e)) return THOR_ERR_ARG;
+  EncPool &P = pool_for(e->device);
+  std::lock_guard<std::mutex> lk(P.mu);
+  for (const EncPool::Pending &q : P.pending)
+    for (thor_enc *x : q.es)
+      if (x == e) return THOR_ERR_ARG;
+  uint8_t *b = e->slots + (long long)e->last_slot * e->slot_bytes;
+  const thor_yuv_planes_t rec = {b + e->offy, b + e->offu, b + e->offv, e->sy, e->sc};
+  SsePair pr;
+  if (!sse_fill_pair(pr, *orig, rec)) return THOR_ERR_ARG;
+  EHIP(hipSetDevice(e->device));
+  return ssim_enqueue(&pr, 1, e->W, e->H, (unsigned long long *)sums_dev, e->stream);
+}
+
 }  // extern "C"
 
 #if defined(THOR_ENC_TRACE)

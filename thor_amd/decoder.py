@@ -111,6 +111,7 @@ class GpuDecoder:
             raise L.create_error("thor_dec_create")
         self._bufs = []
         self._sse_out = None  # device words of sse() (24 bytes, on first use)
+        self._ssim_out = None  # device words of ssim() (24 bytes, on first use)
         self._scalers = {}  # read_scaled: (dw, dh, filter) -> (Scaler, device buffer of one scaled frame)
         self.use_slow_list = True  # False: every k_recon unit in planned order (same output; tests compare both)
 
@@ -119,6 +120,7 @@ class GpuDecoder:
             b.free()
         self._bufs = []
         self._sse_out = None
+        self._ssim_out = None
         for sc, _ in self._scalers.values():
             sc.close()
         self._scalers = {}
@@ -307,6 +309,19 @@ class GpuDecoder:
         out = self._sse_out
         L.check(self.lib.thor_dec_frame_sse(self.h, frame_num, C.byref(planes), out), "thor_dec_frame_sse")
         res = np.empty(3, np.uint64)
+        self.d2h(res, out)
+        return tuple(int(v) for v in res)
+
+    def ssim(self, frame_num: int, planes: L.ThorYuvPlanes):
+        """(Y, U, V) SSIM sums (ints; encoder.ssim_from_sums finishes them) of the
+        resident frame `frame_num` against `planes` (DEVICE pointers), computed on
+        the device (thor_dec_frame_ssim on the context's stream; waits for it).  A
+        frame that is not resident raises with status THOR_ERR_REF."""
+        if self._ssim_out is None:
+            self._ssim_out = self.scratch(24)
+        out = self._ssim_out
+        L.check(self.lib.thor_dec_frame_ssim(self.h, frame_num, C.byref(planes), out), "thor_dec_frame_ssim")
+        res = np.empty(3, np.int64)
         self.d2h(res, out)
         return tuple(int(v) for v in res)
 

@@ -214,6 +214,25 @@ class GpuEncoder:
         """The last ended frame's (Y, U, V) PSNR in dB, as the reference prints it (thor_psnr)."""
         return psnr_i420(self.sse(), self.W, self.H)
 
+    def recon_ssim(self, planes: L.ThorYuvPlanes):
+        """(Y, U, V) SSIM sums (ints; ssim_from_sums finishes them) of the last ended
+        frame's final reconstruction against `planes` (DEVICE pointers), computed on
+        the device (thor_enc_recon_ssim on the encoder's stream; waits for it).  Not
+        before the first frame, and not with a batch or a sequence launch in flight."""
+        out = self.lib.thor_dev_alloc(24)
+        if not out:
+            raise MemoryError("thor_dev_alloc")
+        try:
+            L.check(self.lib.thor_enc_recon_ssim(self.h, C.byref(planes), out), "thor_enc_recon_ssim")
+            # the encoder's stream does not order against the null stream: wait for it (with no
+            # destination thor_enc_read_recon synchronises the stream and copies nothing)
+            L.check(self.lib.thor_enc_read_recon(self.h, None, None, None), "thor_enc_read_recon")
+            res = np.empty(3, np.int64)
+            L.check(self.lib.thor_d2h(res.ctypes.data, out, res.nbytes), "thor_d2h")
+        finally:
+            self.lib.thor_dev_free(out)
+        return tuple(int(v) for v in res)
+
     def encode_all(self) -> bytes:
         return b"".join(self.encode_next() for _ in range(self.num_frames()))
 
@@ -252,6 +271,42 @@ def sse_i420(a, b, width: int, height: int) -> np.ndarray:
     finally:
         lib.thor_dev_free(out)
     return res
+
+
+def ssim_i420(a, b, width: int, height: int, stream=None, wait=None) -> np.ndarray:
+    """thor_ssim_i420 of the plane-set pairs (a[i], b[i]) (ThorYuvPlanes of DEVICE
+    pointers): int64 array (n, 3) of the Y, U, V sums of the windows' quantised
+    SSIM (ssim_from_sums finishes them).  Enqueued on the null
+    stream and waited for; or on `stream` (a hipStream_t as an int), and then
+    `wait` is the caller's way to synchronise that stream (GpuDecoder.sync, a torch
+    stream's synchronize): it is called before the sums are read."""
+    lib = L.load()
+    n = len(a)
+    if n != len(b) or n == 0:
+        raise ValueError("ssim_i420: two non-empty lists of the same length")
+    if stream and wait is None:
+        raise ValueError("ssim_i420: a stream needs `wait` (the read-back does not order against it)")
+    out = lib.thor_dev_alloc(24 * n)
+    if not out:
+        raise MemoryError("thor_dev_alloc")
+    try:
+        L.check(lib.thor_ssim_i420((L.ThorYuvPlanes * n)(*a), (L.ThorYuvPlanes * n)(*b), n, width, height, out, stream),
+                "thor_ssim_i420")
+        if stream:
+            wait()
+        res = np.empty((n, 3), np.int64)
+        L.check(lib.thor_d2h(res.ctypes.data, out, res.nbytes), "thor_d2h")
+    finally:
+        lib.thor_dev_free(out)
+    return res
+
+
+def ssim_from_sums(sums, width: int, height: int):
+    """(Y, U, V, all) SSIM of an I420 frame from its three sums (thor_ssim), all = (4 Y + U + V) / 6."""
+    lib = L.load()
+    dims = ((width, height), (width >> 1, height >> 1), (width >> 1, height >> 1))
+    y, u, v = (float(lib.thor_ssim(int(s), w, h)) for s, (w, h) in zip(sums, dims))
+    return y, u, v, (4 * y + u + v) / 6
 
 
 def encode_batch(encs):

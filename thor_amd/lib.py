@@ -40,6 +40,7 @@ class ThorCsc(C.Structure):
 THOR_RGB8_PACKED, THOR_RGB8_PLANAR, THOR_RGBF32_PLANAR = 0, 1, 2
 THOR_CSC_LAUNCH_IMAGES = 16
 THOR_SCALE_BILINEAR, THOR_SCALE_BICUBIC = 0, 1
+THOR_SSIM_ONE = 1 << 30
 THOR_SCALE_MAX_TAPS, THOR_SCALE_MAX_SIZE, THOR_SCALE_LAUNCH_IMAGES = 33, 8192, 16
 
 
@@ -91,6 +92,7 @@ BATCHED_SYMBOLS = [
     "thor_dev_alloc", "thor_dev_free", "thor_h2d", "thor_d2h", "thor_device_count", "thor_version",
     "thor_last_create_error",
     "thor_sse_i420", "thor_psnr", "thor_dec_frame_sse", "thor_enc_measure_sse", "thor_enc_frame_sse", "thor_enc_seq_sse",
+    "thor_ssim_windows", "thor_ssim_i420", "thor_ssim", "thor_ssim_db", "thor_dec_frame_ssim", "thor_enc_recon_ssim",
     "thor_csc_coeffs", "thor_i420_to_rgb", "thor_rgb_to_i420", "thor_dec_frame_planes", "thor_dec_frame_rgb",
     "thor_scale_taps", "thor_scale_check", "thor_scaler_create", "thor_scaler_destroy", "thor_scale_i420",
     "thor_dec_frame_scaled",
@@ -273,6 +275,19 @@ def load(path: str = LIB_PATH):
     L.thor_enc_frame_sse.restype = i
     L.thor_enc_seq_sse.argtypes = [P, i, i, C.POINTER(C.c_uint64)]
     L.thor_enc_seq_sse.restype = i
+    # frame quality (SSIM on the device)
+    L.thor_ssim_windows.argtypes = [i, i]
+    L.thor_ssim_windows.restype = i
+    L.thor_ssim_i420.argtypes = [C.POINTER(ThorYuvPlanes), C.POINTER(ThorYuvPlanes), i, i, i, P, P]
+    L.thor_ssim_i420.restype = i
+    L.thor_ssim.argtypes = [C.c_int64, i, i]
+    L.thor_ssim.restype = C.c_double
+    L.thor_ssim_db.argtypes = [C.c_double]
+    L.thor_ssim_db.restype = C.c_double
+    L.thor_dec_frame_ssim.argtypes = [P, i, C.POINTER(ThorYuvPlanes), P]
+    L.thor_dec_frame_ssim.restype = i
+    L.thor_enc_recon_ssim.argtypes = [P, C.POINTER(ThorYuvPlanes), P]
+    L.thor_enc_recon_ssim.restype = i
     # colour conversion (I420 <-> RGB images on the device)
     L.thor_csc_coeffs.argtypes = [i, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.thor_csc_coeffs.restype = i
