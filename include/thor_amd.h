@@ -675,6 +675,51 @@ int thor_dec_frame_ssim(thor_dec_t *d, int frame_num, const thor_yuv_planes_t *o
  * launch overwrites, are not measurable this way. */
 int thor_enc_recon_ssim(thor_enc_t *e, const thor_yuv_planes_t *orig, int64_t *sums_dev);
 
+/* ---- frame analysis: lookahead costs and scene cuts on the device ---------- *
+ * What a frame will cost before it is coded, and whether a new scene starts
+ * with it: cheap intra and inter costs on a half-resolution copy of the luma,
+ * computed where the frames live (k_lookahead, thor_amd/csrc/lookahead.hip).
+ * The reference has no lookahead: the arithmetic is specified in integers
+ *  and is bit-exact on every run and every launch shape.
+ * Only luma is read (the u / v pointers of a plane set may be NULL).
+ *
+ * lowres: lw = width >> 1, lh = height >> 1, L[y][x] = (p[2y][2x] + p[2y][2x+1]
+ *   + p[2y+1][2x] + p[2y+1][2x+1] + 2) >> 2, of both frames.
+ * blocks: 8x8 lowres pixels (16x16 source pixels), bw = lw >> 3, bh = lh >> 3.
+ * satd(d) = (sum |H d H^T| + 2) >> 2, H the 8x8 Hadamard matrix (<= 32 640).
+ * intra: the least satd of cur minus DC ((top8 + left8 + 8) >> 4; one
+ *   neighbour (sum + 4) >> 3; none 128), V (the row above, not in the first
+ *   block row) and H (the column to the left, not in the first block column),
+ *   the neighbours being cur's own lowres pixels.
+ * inter: full search of (dy, dx) in [-8, 8]^2 on ref's lowres plane,
+ *   coordinates clamped to it; the least key sad << 14 | (|dx| + |dy|) << 9 |
+ *   ((dy + 8) * 17 + (dx + 8)) wins (least SAD, then the shortest vector, then
+ *   raster order); inter = satd(cur - ref block at the winner).
+ * A pair whose ref[i].y is NULL (or ref itself NULL) is intra-only:
+ *   inter = intra, sad = 0xFFFF, mv = (0, 0). */
+typedef struct thor_la_block {
+  uint16_t intra, inter, sad; /* sad: the winner's */
+  int8_t mvx, mvy;            /* in lowres pixels: the source displacement is twice that */
+} thor_la_block_t;            /* 8 bytes, little-endian */
+/* bw * bh, and the two through the pointers (either may be NULL);
+ * THOR_ERR_ARG outside 16 <= width, height <= 16384. */
+int thor_lookahead_blocks(int width, int height, int *bw, int *bh);
+/* Frame pair i: cur[i] against ref[i].  cur / ref: HOST arrays of n plane sets
+ * (DEVICE pointers, own strides, any alignment).  blocks_dev: DEVICE, n * bw * bh
+ * records in raster order per frame, 8-byte aligned, overwritten; may be NULL.
+ * sums_dev: DEVICE, 4 * n uint64, overwritten: sum of intra, sum of inter, sum
+ * of min(intra, inter), number of blocks with intra < inter.  16 <= width,
+ * height <= 16384, 1 <= n <= 65535, cur and every cur[i].y non-NULL, luma strides
+ * >= width, else THOR_ERR_ARG before any device call.  Enqueued on `stream`;
+ * returns without waiting (thor_d2h_stream reads the results behind it). */
+int thor_lookahead_i420(const thor_yuv_planes_t *cur, const thor_yuv_planes_t *ref, int n, int width, int height,
+                        thor_la_block_t *blocks_dev, uint64_t *sums_dev, void *stream);
+/* Host arithmetic on one frame's four sums: 1 when sums[0] > 0 and
+ * 100 * sums[2] >= percent * sums[0] (the frame is hardly cheaper to predict
+ * from its reference than from itself), else 0; THOR_ERR_ARG unless
+ * 1 <= percent <= 100.  The threshold is the caller's. */
+int thor_lookahead_scenecut(const uint64_t sums[4], int percent);
+
 /* ---- colour conversion: I420 <-> RGB on the device ------------------------ *
  * RGB images in HBM in and out of the codec (k_csc_to_rgb / k_csc_from_rgb,
  * thor_amd/csrc/color.hip).  The arithmetic is specified in integers (DESIGN.md
@@ -790,6 +835,12 @@ void *thor_dev_alloc(size_t bytes);
 int thor_dev_free(void *p);
 int thor_h2d(void *dst, const void *src, size_t bytes);
 int thor_d2h(void *dst, const void *src, size_t bytes);
+/* thor_d2h behind the work queued on `stream` (a hipStream_t of the calling
+ * thread's current device): copied on that stream, and the call waits for the
+ * copy -- so for what was enqueued there before it and for nothing else.  The
+ * way to read a result off a non-blocking stream, which thor_d2h does not order
+ * against.  THOR_ERR_ARG for a NULL pointer or no bytes. */
+int thor_d2h_stream(void *dst, const void *src, size_t bytes, void *stream);
 int thor_device_count(void);
 const char *thor_version(void);
 

@@ -130,6 +130,12 @@ int thor_d2h(void *dst, const void *src, size_t bytes) {
   HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
   return THOR_OK;
 }
+int thor_d2h_stream(void *dst, const void *src, size_t bytes, void *stream) {
+  if (!dst || !src || !bytes) return THOR_ERR_ARG;
+  HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  return THOR_OK;
+}
 
 int thor_last_create_error(size_t *bytes, char *msg, size_t cap) {
   if (bytes) *bytes = g_create_err.bytes;

@@ -233,6 +233,18 @@ class GpuEncoder:
             self.lib.thor_dev_free(out)
         return tuple(int(v) for v in res)
 
+    def input_costs(self, blocks: bool = False):
+        """Lookahead costs of the input sequence this encoder holds (upload_sequence,
+        use_device_sequence, set_input_rgb, set_input_scaled): lookahead.sequence_costs
+        on the encoder's stream, so behind a conversion or scaling queued there.
+        uint64 (n, 4) per frame in display order, frame 0 intra-only.  Reads the input
+        only: nothing in the encode path calls it, and the coded bytes do not change."""
+        from . import lookahead
+
+        if not self.seq_dev or self.nin <= 0:
+            raise ValueError("input_costs: no input sequence")
+        return lookahead.sequence_costs(self.seq_dev, self.nin, self.W, self.H, blocks, self.stream())
+
     def encode_all(self) -> bytes:
         return b"".join(self.encode_next() for _ in range(self.num_frames()))
 

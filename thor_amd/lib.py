@@ -41,6 +41,7 @@ THOR_RGB8_PACKED, THOR_RGB8_PLANAR, THOR_RGBF32_PLANAR = 0, 1, 2
 THOR_CSC_LAUNCH_IMAGES = 16
 THOR_SCALE_BILINEAR, THOR_SCALE_BICUBIC = 0, 1
 THOR_SSIM_ONE = 1 << 30
+THOR_LA_NO_SAD = 0xFFFF  # thor_la_block_t.sad of an intra-only pair
 THOR_SCALE_MAX_TAPS, THOR_SCALE_MAX_SIZE, THOR_SCALE_LAUNCH_IMAGES = 33, 8192, 16
 
 
@@ -89,10 +90,11 @@ BATCHED_SYMBOLS = [
     "thor_enc_read_recon", "thor_enc_reset", "thor_enc_debug_stall", "thor_enc_record_sb_costs", "thor_enc_sb_costs",
     "thor_parser_create", "thor_parser_destroy", "thor_parser_seq", "thor_parse_frame", "thor_frame_image",
     "thor_ti_create", "thor_ti_destroy", "thor_interpolate_frames", "thor_ti_read_fields", "thor_ti_status",
-    "thor_dev_alloc", "thor_dev_free", "thor_h2d", "thor_d2h", "thor_device_count", "thor_version",
+    "thor_dev_alloc", "thor_dev_free", "thor_h2d", "thor_d2h", "thor_d2h_stream", "thor_device_count", "thor_version",
     "thor_last_create_error",
     "thor_sse_i420", "thor_psnr", "thor_dec_frame_sse", "thor_enc_measure_sse", "thor_enc_frame_sse", "thor_enc_seq_sse",
     "thor_ssim_windows", "thor_ssim_i420", "thor_ssim", "thor_ssim_db", "thor_dec_frame_ssim", "thor_enc_recon_ssim",
+    "thor_lookahead_blocks", "thor_lookahead_i420", "thor_lookahead_scenecut",
     "thor_csc_coeffs", "thor_i420_to_rgb", "thor_rgb_to_i420", "thor_dec_frame_planes", "thor_dec_frame_rgb",
     "thor_scale_taps", "thor_scale_check", "thor_scaler_create", "thor_scaler_destroy", "thor_scale_i420",
     "thor_dec_frame_scaled",
@@ -288,6 +290,13 @@ def load(path: str = LIB_PATH):
     L.thor_dec_frame_ssim.restype = i
     L.thor_enc_recon_ssim.argtypes = [P, C.POINTER(ThorYuvPlanes), P]
     L.thor_enc_recon_ssim.restype = i
+    # frame analysis (lookahead costs and scene cuts on the device)
+    L.thor_lookahead_blocks.argtypes = [i, i, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.thor_lookahead_blocks.restype = i
+    L.thor_lookahead_i420.argtypes = [C.POINTER(ThorYuvPlanes), C.POINTER(ThorYuvPlanes), i, i, i, P, P, P]
+    L.thor_lookahead_i420.restype = i
+    L.thor_lookahead_scenecut.argtypes = [C.POINTER(C.c_uint64), i]
+    L.thor_lookahead_scenecut.restype = i
     # colour conversion (I420 <-> RGB images on the device)
     L.thor_csc_coeffs.argtypes = [i, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.thor_csc_coeffs.restype = i
@@ -339,6 +348,8 @@ def load(path: str = LIB_PATH):
     L.thor_h2d.restype = i
     L.thor_d2h.argtypes = [P, P, C.c_size_t]
     L.thor_d2h.restype = i
+    L.thor_d2h_stream.argtypes = [P, P, C.c_size_t, P]
+    L.thor_d2h_stream.restype = i
     L.thor_last_create_error.argtypes = [C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]
     L.thor_last_create_error.restype = i
     _lib = L
