@@ -830,6 +830,73 @@ int thor_scale_i420(thor_scaler_t *s, const thor_yuv_planes_t *src, const thor_y
  * when the frame is not resident. */
 int thor_dec_frame_scaled(thor_dec_t *d, int frame_num, thor_scaler_t *s, const thor_yuv_planes_t *dst);
 
+/* ---- temporal denoise: a motion-compensated pre-filter of the source ------- *
+ * Camera noise taken out of the frames before they are coded, where they live
+ * (k_tf_luma / k_tf_chroma, thor_amd/csrc/tf.hip).  The reference has no such
+ * filter: the arithmetic is specified in integers and is
+ * bit-exact on every run and every launch shape.  Nothing in the encode path
+ * calls it unless the caller asks.
+ *
+ * Frames: 8-bit I420, width and height multiples of 8 in 16 .. 16384.  A target
+ * T and nrefs (1 .. 4) references of the same size; a reference whose y is NULL
+ * is absent and contributes nothing.  Reference coordinates are clamped to the
+ * plane; >> of a negative number is arithmetic.
+ * prediction of an n x n block at (x, y) at a half-pel vector (mvx, mvy) of its
+ *   plane: from a = R[y + (mvy >> 1)][x + (mvx >> 1)], b its right neighbour, c
+ *   the pixel below, d below right: a; (a + b + 1) >> 1 (mvx odd);
+ *   (a + c + 1) >> 1 (mvy odd); (a + b + c + d + 2) >> 2 (both).
+ * motion, per reference and 8x8 luma block (bx, by): the start is twice the
+ *   vector of thor_lookahead_i420(T, R) at (bx >> 1, by >> 1), or (0, 0) outside
+ *   that grid; then (dy, dx) in [-2, 2]^2 integer pixels, least key
+ *   sad << 10 | (|dx| + |dy|) << 5 | ((dy + 2) * 5 + dx + 2); then (hy, hx) in
+ *   {-1, 0, 1}^2 half pels around twice that, least key
+ *   sad << 6 | (|hx| + |hy|) << 4 | ((hy + 1) * 3 + hx + 1).
+ * chroma: the 4x4 block under an 8x8 luma block uses (mvx >> 1, mvy >> 1) as a
+ *   half-pel vector of the chroma plane.
+ * blend, per plane and pixel p: d = T[p] - P_r[p], e_r the block's SSD on that
+ *   plane >> 6 (luma 8x8) or >> 4 (chroma 4x4), m = (d d + e_r) >> 1,
+ *   k = min(63, (min(m, 2047) * mult) >> 16), w_r = LUT[k],
+ *   out = (256 T + sum w_r P_r + (den >> 1)) / den, den = 256 + sum w_r;
+ *   mult = thor_tf_mult(strength), one strength for luma and one for chroma;
+ *   LUT[k] = floor(256 exp(-k / 16) + 1/2), LUT[63] = 0 (the table is in sec. 7g). */
+#define THOR_TF_MAX_REFS 4
+#define THOR_TF_MAX_TARGETS 4096
+typedef struct thor_tf_record {
+  int8_t mvx, mvy; /* half-pel units of the luma plane, |.| <= 37 */
+  uint16_t e;      /* SSD(T block, prediction) >> 6 */
+} thor_tf_record_t; /* 4 bytes, little-endian; zero for an absent reference */
+typedef struct thor_tf thor_tf_t;
+
+/* Host, no device: THOR_OK when frames of this size can be filtered from nrefs
+ * references, THOR_ERR_ARG otherwise. */
+int thor_tf_check(int width, int height, int nrefs);
+/* Host, no device: mult = ((16 << 16) + (s s >> 1)) / (s s) of a strength s in
+ * 1 .. 64; THOR_ERR_ARG outside. */
+int thor_tf_mult(int strength);
+/* bw8 * bh8 = (width >> 3) * (height >> 3), and the two through the pointers
+ * (either may be NULL); THOR_ERR_ARG for a size thor_tf_check refuses. */
+int thor_tf_blocks(int width, int height, int *bw8, int *bh8);
+/* A filter of one frame size for calls of at most max_targets (1 .. 4096)
+ * targets: owns the lookahead records and sums of the coarse stage and the
+ * records of a call that asks for none.  NULL on failure
+ * (thor_last_create_error). */
+thor_tf_t *thor_tf_create(int width, int height, int max_targets, int device);
+void thor_tf_destroy(thor_tf_t *t);
+/* n targets in one call: cur / dst are HOST arrays of n plane sets, refs of
+ * n * nrefs, target-major (DEVICE pointers, own strides, any alignment); a
+ * reference with a NULL y is absent.  mv_dev: DEVICE, n * nrefs * bw8 * bh8
+ * records, reference-major within a target, raster order, 4-byte aligned,
+ * overwritten; may be NULL.  Only the width x height (chroma: halved) samples
+ * of dst are written.  THOR_ERR_ARG -- before any device call -- for nrefs
+ * outside 1 .. 4, a strength outside 1 .. 64, n outside 1 .. max_targets, a NULL
+ * cur / dst plane or a present reference's NULL chroma plane, a stride below a
+ * row, and a dst plane equal to its cur plane or to one of its references'
+ * planes (the filter is not in place).  Two calls on one context must not
+ * overlap (they share its workspace).  Enqueued on `stream`; returns without
+ * waiting. */
+int thor_tf_i420(thor_tf_t *t, const thor_yuv_planes_t *cur, const thor_yuv_planes_t *refs, const thor_yuv_planes_t *dst,
+                 int n, int nrefs, int strength_y, int strength_c, thor_tf_record_t *mv_dev, void *stream);
+
 /* ---- device memory helpers (so the C-ABI is usable without torch) ------ */
 void *thor_dev_alloc(size_t bytes);
 int thor_dev_free(void *p);

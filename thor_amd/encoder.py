@@ -146,6 +146,33 @@ class GpuEncoder:
             self.lib.thor_dev_free(self.seq_dev)
         self.seq_dev, self.own_seq, self.nin = seq, True, nframes
 
+    def filter_input(self, radius: int = 2, strength=(8, 3)):
+        """Replace the input sequence this encoder holds (upload_sequence,
+        use_device_sequence, set_input_rgb, set_input_scaled) by a temporally
+        denoised, owned copy (tfilter.filter_sequence): frame k
+        filtered from the unfiltered frames k - radius .. k + radius that exist.
+        Runs on the encoder's stream, so behind a scaling queued there, and waits
+        for it; the old buffer is freed after that, if the encoder owned it.  The
+        default strengths (luma, chroma) are twice the synthetic test clip's noise
+        sigma, rounded: a starting point, not a tuned value.  Nothing in the encode
+        path calls this: without it the coded bytes do not change."""
+        from . import tfilter
+
+        if not self.seq_dev or self.nin <= 0:
+            raise ValueError("filter_input: no input sequence")
+        seq = self.lib.thor_dev_alloc(self.nin * self.fsize)
+        if not seq:
+            raise MemoryError("thor_dev_alloc")
+        try:
+            tfilter.filter_sequence(self.seq_dev, seq, self.nin, self.W, self.H, radius, strength, self.stream(),
+                                    device=self.device)
+        except Exception:
+            self.lib.thor_dev_free(seq)
+            raise
+        if self.own_seq:
+            self.lib.thor_dev_free(self.seq_dev)
+        self.seq_dev, self.own_seq = seq, True
+
     def reset(self):
         """Start the sequence again (thor_enc_reset): same input, same .bit."""
         L.check(self.lib.thor_enc_reset(self.h), "thor_enc_reset")

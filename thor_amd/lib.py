@@ -42,6 +42,7 @@ THOR_CSC_LAUNCH_IMAGES = 16
 THOR_SCALE_BILINEAR, THOR_SCALE_BICUBIC = 0, 1
 THOR_SSIM_ONE = 1 << 30
 THOR_LA_NO_SAD = 0xFFFF  # thor_la_block_t.sad of an intra-only pair
+THOR_TF_MAX_REFS, THOR_TF_MAX_TARGETS = 4, 4096
 THOR_SCALE_MAX_TAPS, THOR_SCALE_MAX_SIZE, THOR_SCALE_LAUNCH_IMAGES = 33, 8192, 16
 
 
@@ -98,6 +99,7 @@ BATCHED_SYMBOLS = [
     "thor_csc_coeffs", "thor_i420_to_rgb", "thor_rgb_to_i420", "thor_dec_frame_planes", "thor_dec_frame_rgb",
     "thor_scale_taps", "thor_scale_check", "thor_scaler_create", "thor_scaler_destroy", "thor_scale_i420",
     "thor_dec_frame_scaled",
+    "thor_tf_check", "thor_tf_mult", "thor_tf_blocks", "thor_tf_create", "thor_tf_destroy", "thor_tf_i420",
 ]
 L2_SURFACE_SYMBOLS = ["deblock_frame_y", "deblock_frame_uv", "make_top_and_left", "get_intra_prediction", "dequantize",
                       "reconstruct_block", "quantize"]
@@ -320,6 +322,19 @@ def load(path: str = LIB_PATH):
     L.thor_scale_i420.restype = i
     L.thor_dec_frame_scaled.argtypes = [P, i, P, C.POINTER(ThorYuvPlanes)]
     L.thor_dec_frame_scaled.restype = i
+    # temporal denoise (motion-compensated pre-filter of I420 frames on the device)
+    L.thor_tf_check.argtypes = [i, i, i]
+    L.thor_tf_check.restype = i
+    L.thor_tf_mult.argtypes = [i]
+    L.thor_tf_mult.restype = i
+    L.thor_tf_blocks.argtypes = [i, i, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.thor_tf_blocks.restype = i
+    L.thor_tf_create.argtypes = [i, i, i, i]
+    L.thor_tf_create.restype = P
+    L.thor_tf_destroy.argtypes = [P]
+    L.thor_tf_i420.argtypes = [P, C.POINTER(ThorYuvPlanes), C.POINTER(ThorYuvPlanes), C.POINTER(ThorYuvPlanes), i, i, i, i,
+                               P, P]
+    L.thor_tf_i420.restype = i
     # the reference's SIMD kernel surface (include/thor_kernels.h)
     u8p = P
     L.transform_simd.argtypes = [P, P, i, i]
