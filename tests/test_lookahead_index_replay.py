@@ -18,8 +18,7 @@ SRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 
 def _defines():
     env = {}
     for name, expr in re.findall(r"^#define (LA_[A-Z_]+) ([^/\n]+?)\s*(?://.*)?$", open(SRC).read(), re.M):
-        if name != "LA_KNOCK":
-            env[name] = eval(expr, {}, env)  # (the defines are integer expressions of earlier defines)
+        env[name] = eval(expr, {}, env)  # (the defines are integer expressions of earlier defines)
     return env
 
 

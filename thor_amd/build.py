@@ -17,8 +17,6 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp
 # with the accumulate-in-place VOP2 forms (v_dot4c / v_dot2c) available hipcc seeds every
 # chain with a v_mov (k_recon: ~3 700 of them).  The host pass ignores these (it warns).
 FLAGS += ["-Xclang", "-target-feature", "-Xclang", "-dot6-insts", "-Xclang", "-target-feature", "-Xclang", "-dot4-insts"]
-# k_recon: 5 waves per SIMD (96 VGPRs; a few spills on the per-cell path only)
-FLAGS += ["-DRECON_WPE=5"]
 # No interprocedural register allocation: with it (the AMDGPU default) a caller of
 # the encoder's non-inlined RD functions allocates against each callee's actual
 # clobber set, and a register-hungry callee (the candidate-parallel motion search)

@@ -1107,29 +1107,9 @@ TE_FN int te_quant_t(TeTx &X, int qp, int size, int type, int16_t *coef, int rdo
   return cbp;
 }
 TE_FN int te_quant(TeTx &X, int qp, int size, int type, int rdoq) { return te_quant_t(X, qp, size, type, nullptr, rdoq); }
-
-// dequantize (common/common_block.c:132-146), int16 truncating store, in place
-TE_FN void te_dequant(TeTx &X, int qp, int size) {
-  const int q = TE_MIN(size, 16);
-  const int rshift = te_log2(size) - 1, add = 1 << (rshift - 1);
-  const int lshift = qp / 6, scale = te_gdequant[qp % 6];
-  for (int e = TE_LANE; e < q * q; e += TE_NL) X.C[e] = (int16_t)te_wrap16(((X.C[e] * scale) * (1 << lshift) + add) >> rshift);
-  te_sync();
-}
-#ifndef TE_QUANT_FUSE
-#define TE_QUANT_FUSE 1
-#endif
 // quantize -> the levels into the candidate's tile -> X.C dequantized (when cbp)
 TE_FN int te_quant_chain(TeTx &X, int qp, int size, int type, int16_t *coef, int rdoq) {
-#if TE_QUANT_FUSE
   return te_quant_t(X, qp, size, type, coef, rdoq);
-#else
-  const int cbp = te_quant(X, qp, size, type, rdoq);
-  const int q = TE_MIN(size, 16);
-  for (int e = TE_LANE; e < q * q; e += TE_NL) coef[e] = (int16_t)X.C[e];
-  if (cbp) te_dequant(X, qp, size);
-  return cbp;
-#endif
 }
 
 // inverse_transform (common/transform.c:432-518): X.C (q x q) -> X.R

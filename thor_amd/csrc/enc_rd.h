@@ -984,8 +984,7 @@ TE_FN int te_encode_block_t(const TeFrame &F_, TeBits &b_, TeBlockInfo &bi_, TeP
   if (tb_split) p.cbp_y = p.cbp_u = p.cbp_v = 1;  // deblocking only (:1781-1784)
   return nbits;
 }
-// The two out-of-line copies (one call frame each; the I-frame copy may also be
-// inlined where it has a single call site, TE_EB1_INLINE)
+// The two out-of-line copies (one call frame each)
 TE_NOINL int te_encode_block_i(const TeFrame &F, TeBits &b, TeBlockInfo &bi, TeParam &p) {
   return te_encode_block_t<true>(F, b, bi, p);
 }
@@ -995,11 +994,6 @@ TE_NOINL int te_encode_block_p(const TeFrame &F, TeBits &b, TeBlockInfo &bi, TeP
 TE_FN int te_encode_block(const TeFrame &F, TeBits &b, TeBlockInfo &bi, TeParam &p) {
   return te_lds(&F)->frame_type == TE_I ? te_encode_block_i(F, b, bi, p) : te_encode_block_p(F, b, bi, p);
 }
-#ifdef TE_EB1_INLINE
-#define TE_ENCODE_I te_encode_block_t<true>
-#else
-#define TE_ENCODE_I te_encode_block_i
-#endif
 // The final encode of a block with its best parameters bi.bp (process_block,
 // enc/encode_block.c:2953-2962 / 3012-3018).  Without tb-split the best
 // candidate's reconstruction is in rec_best and (usually) its syntax bits in
@@ -2173,39 +2167,6 @@ TE_FN uint32_t te_mode_decision_intra(const TeFrame &F_, TeBlockInfo &bi_, TeBit
   const int ntb = bi.max_num_tb_part, nrdo = F.intra_rdo ? F.num_intra_modes * ntb : 0;
   uint32_t min_icost = TE_MAX_UINT32;
   int best_mode = TE_DC;
-#ifdef TE_MDI_TWO
-  if (F.intra_rdo) {
-    for (int im = TE_DC; im < F.num_intra_modes; im++) {
-      tmp.intra_mode = im;
-      for (int tbp = 0; tbp < ntb; tbp++) {
-        tmp.tb_param = tbp;
-        tmp.mode = TE_INTRA;
-        const int nbits = TE_ENCODE_I(F, b, bi, tmp);
-        cost = te_cost(F, bi, bi.rec, size, size, nbits);
-        if (cost < min_icost) {
-          min_icost = cost;
-          best_mode = im;
-        }
-      }
-    }
-    intra_mode = best_mode;
-  } else {
-    te_search_intra(F, bi, F.num_intra_modes, &intra_mode);
-  }
-  tmp.intra_mode = intra_mode;
-  for (int tbp = 0; tbp < ntb; tbp++) {
-    tmp.tb_param = tbp;
-    tmp.mode = TE_INTRA;
-    const int nbits = TE_ENCODE_I(F, b, bi, tmp);
-    cost = te_cost(F, bi, bi.rec, size, size, nbits);
-    if (cost < min_cost) {
-      min_cost = cost;
-      te_copy_best(bi, tmp);
-      te_keep_best_bits(b, bi, nbits);
-    }
-  }
-  (void)nrdo;
-#else
   if (!F.intra_rdo) te_search_intra(F, bi, F.num_intra_modes, &intra_mode);
   for (int st = 0; st < nrdo + ntb; st++) {
     const bool rdo = st < nrdo;
@@ -2214,7 +2175,7 @@ TE_FN uint32_t te_mode_decision_intra(const TeFrame &F_, TeBlockInfo &bi_, TeBit
     tmp.intra_mode = im;
     tmp.tb_param = rdo ? st - (st / ntb) * ntb : st - nrdo;
     tmp.mode = TE_INTRA;
-    const int nbits = TE_ENCODE_I(F, b, bi, tmp);
+    const int nbits = te_encode_block_i(F, b, bi, tmp);
     cost = te_cost(F, bi, bi.rec, size, size, nbits);
     if (rdo) {
       if (cost < min_icost) {
@@ -2227,7 +2188,6 @@ TE_FN uint32_t te_mode_decision_intra(const TeFrame &F_, TeBlockInfo &bi_, TeBit
       te_keep_best_bits(b, bi, nbits);
     }
   }
-#endif
   te_rewind(b, pos_ref);  // rewind (:2476)
   TE_TR(F.frame_num, 5, bi.ypos, bi.xpos, size, min_cost, bi.bp.mode, TE_MAX_UINT32);
   return min_cost;
@@ -2630,12 +2590,7 @@ TE_FN int te_es_chroma(const uint8_t *org, int os, int size, const uint8_t *pb, 
 }
 
 // check_early_skip_block, :2613-2741.  Returns 1 when every sub-block is insignificant.
-#ifdef TE_ES_INLINE
-TE_FN
-#else
-TE_NOINL
-#endif
-int te_check_early_skip(const TeFrame &F_, const TeBlockInfo &bi_, const TeParam &p_) {
+TE_NOINL int te_check_early_skip(const TeFrame &F_, const TeBlockInfo &bi_, const TeParam &p_) {
   const TeFrame &F = *te_lds(&F_);
   const TeScratch S = te_here();
   const TeBlockInfo &bi = *te_lds(&bi_);
@@ -2766,13 +2721,8 @@ TE_NOINL int te_search_early_skip(const TeFrame &F_, TeSB &sb_, TeBlockInfo &bi_
 // te_commit_block); F.leaf8 = 0 (THOR_ENC_LEAF8=0) keeps that path.
 // A call, not inlined into process_block: inlined, its live ranges on top of the three quadtree
 // levels' grew k_enc_rows' scratch frame (2 192 -> 2 672 B per lane).
-#ifdef TE_LEAF8_INLINE
-#define TE_LEAF8_FN TE_FN
-#else
-#define TE_LEAF8_FN TE_NOINL
-#endif
 __shared__ unsigned g_te_leaf8_n;  // CUs this worker coded here (k_enc_rows sums it into its profile)
-TE_LEAF8_FN uint32_t te_leaf8_intra(const TeFrame &F_, TeSB &sb_, TeBlockInfo &bi_) {
+TE_NOINL uint32_t te_leaf8_intra(const TeFrame &F_, TeSB &sb_, TeBlockInfo &bi_) {
   const TeFrame &F = *te_lds(&F_);
   TeSB &sb = *te_lds(&sb_);
   TeBlockInfo &bi = *te_lds(&bi_);

@@ -73,10 +73,7 @@ struct TsArgs {
   TeScratchMem *scratch;
   unsigned *ctl, *items, *err;
   unsigned qoff[TS_NCLS];
-  unsigned qtot[TS_NCLS];    // tasks of each class (ticket claims past it find nothing)
-  int ncls;                  // classes in use (stream i -> class i * ncls / n)
-  int claim;                 // 0: compare-and-swap claims (never block), 1: tickets (a claim may wait for its slot)
-  unsigned total;            // tasks of the launch
+  unsigned total;           // tasks of the launch
   unsigned n_ijobs;          // I-frame jobs (idle workers may retire once they are all done)
   int min_alive;
   unsigned long long spin_limit, retire_ticks;
@@ -100,33 +97,26 @@ __device__ __forceinline__ void ts_dep(const TsArgs &A, unsigned *cnt, unsigned 
   if (old + 1 == need) ts_push(A, cls, item);
 }
 // (lane 0) the oldest ready task of the highest class with one, TE_Q_EMPTY if none.
-// claim 0: a slot below the tail is taken by compare-and-swap on the head
-// (never waits; contended when many idle workers race for one item);
-// claim 1: a ticket (one fetch-and-add) as soon as the class looks non-empty --
-// a ticket past the items pushed so far waits for its slot (every slot below
-// the class's task count fills: its tasks depend only on its own), one past
-// the class's task count is dropped.
+// A slot below the tail is taken by compare-and-swap on the head (never waits
+// for a slot that may not fill; contended when many idle workers race for one
+// item).  The class loop stays rolled: unrolled, the 16 compare-and-swap loops
+// nearly double k_enc_seq's text.
 __device__ __forceinline__ unsigned ts_pop(const TsArgs &A, unsigned long long &fails, unsigned long long &waits) {
-  for (int c = 0; c < A.ncls; c++) {
+#pragma unroll 1
+  for (int c = 0; c < TS_NCLS; c++) {
     unsigned h = te_ld_relaxed(&A.ctl[TS_HEAD(c)]);
-    if (A.claim) {
-      if (h >= A.qtot[c] || h >= te_ld_relaxed(&A.ctl[TS_TAIL(c)])) continue;
-      h = __hip_atomic_fetch_add(&A.ctl[TS_HEAD(c)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (h >= A.qtot[c]) continue;
-    } else {
-      bool got = false;
-      for (;;) {
-        const unsigned t = te_ld_relaxed(&A.ctl[TS_TAIL(c)]);
-        if (h >= t) break;
-        if (__hip_atomic_compare_exchange_strong(&A.ctl[TS_HEAD(c)], &h, h + 1, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT)) {
-          got = true;
-          break;
-        }
-        fails++;  // h now holds the head another worker moved it to
+    bool got = false;
+    for (;;) {
+      const unsigned t = te_ld_relaxed(&A.ctl[TS_TAIL(c)]);
+      if (h >= t) break;
+      if (__hip_atomic_compare_exchange_strong(&A.ctl[TS_HEAD(c)], &h, h + 1, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_AGENT)) {
+        got = true;
+        break;
       }
-      if (!got) continue;
+      fails++;  // h now holds the head another worker moved it to
     }
+    if (!got) continue;
     unsigned item;
     const unsigned long long w0 = __builtin_amdgcn_s_memrealtime();
     while ((item = te_ld_relaxed(&A.items[A.qoff[c] + h])) == TE_Q_EMPTY) __builtin_amdgcn_s_sleep(4);
@@ -621,15 +611,6 @@ int thor_enc_seq_begin(thor_enc_t *const *es, int n, int nframes, const uint8_t 
     EHIP(hipHostMalloc((void **)&S.arena, aw * 4 + 64, hipHostMallocCoherent | hipHostMallocMapped));
     S.arena_words = aw;
   }
-  // scheduling knobs (experiments): THOR_SEQ_CLASSES (1..16, default 16), THOR_SEQ_CLAIM
-  // (0 compare-and-swap, 1 tickets), THOR_SEQ_RETIRE (0: workers never leave early)
-  auto knob = [](const char *name, int dflt) {
-    const char *v = getenv(name);
-    return v && *v ? atoi(v) : dflt;
-  };
-  int ncls = knob("THOR_SEQ_CLASSES", TS_NCLS);
-  ncls = ncls < 1 ? 1 : (ncls > TS_NCLS ? TS_NCLS : ncls);
-  const int prio = knob("THOR_SEQ_PRIO", 0) && ncls >= 3;
   // the jobs: each context's frames in coding order, its host state advanced frame by frame
   hipStream_t st = lead->stream;
   std::vector<TsJob> jobs(njobs);
@@ -660,7 +641,7 @@ int thor_enc_seq_begin(thor_enc_t *const *es, int n, int nframes, const uint8_t 
   };
   for (int i = 0; i < n; i++) {
     thor_enc *e = es[i];
-    const int cls = (int)((long long)i * ncls / n);
+    const int cls = (int)((long long)i * TS_NCLS / n);  // classes: stream groups
     for (int f = 0; f < nframes; f++) {
       const int jx = i * nframes + f;
       TsJob &T = jobs[jx];
@@ -687,14 +668,8 @@ int thor_enc_seq_begin(thor_enc_t *const *es, int n, int nframes, const uint8_t 
       T.dst = orig;
       T.next = f + 1 < nframes ? jx + 1 : -1;
       T.next2 = f + 2 < nframes ? jx + 2 : -1;
-      // classes: stream groups (THOR_SEQ_PRIO 0), or by task kind (1): the loop filters, packing and
-      // input copies first (a frame's hand-off to the next), then P-frame SBs, then I-frame SBs by stream group
       T.cls = cls;
       T.aux = cls;
-      if (prio) {
-        T.aux = 0;
-        T.cls = pl.frame_type != TE_I ? 1 : 2 + (int)((long long)i * (ncls - 2) / n);
-      }
       T.need0 = (fetch ? nsbv : 0) + (f > 0) + (f > 1);
       T.is_i = pl.frame_type == TE_I;
       uint8_t *cs = e->slots + (long long)cur * e->slot_bytes;
@@ -773,17 +748,12 @@ int thor_enc_seq_begin(thor_enc_t *const *es, int n, int nframes, const uint8_t 
   A.ctl = S.ctl;
   A.items = S.items;
   A.err = P.err;
-  for (int c = 0; c < TS_NCLS; c++) {
-    A.qoff[c] = qoff[c];
-    A.qtot[c] = qn[c];
-  }
-  A.ncls = ncls;
-  A.claim = knob("THOR_SEQ_CLAIM", 0);
+  for (int c = 0; c < TS_NCLS; c++) A.qoff[c] = qoff[c];
   A.total = total;
   A.n_ijobs = n_i;
   A.min_alive = nwork / 2;
   A.spin_limit = g_spin_limit.load();
-  A.retire_ticks = knob("THOR_SEQ_RETIRE", 1) ? 50000 : ~0ULL >> 1;  // 0.5 ms without a ready task
+  A.retire_ticks = 50000;  // 0.5 ms without a ready task
   A.arena = S.arena;
   A.arena_words = S.arena_words;
   A.meta = S.meta;

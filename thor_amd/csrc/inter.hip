@@ -38,10 +38,6 @@
 
 #include "common.h"
 
-#ifndef RECON_PROBE
-#define RECON_PROBE 0  // timing-only probe builds (tools/gpu_var.sh); 0 in the product
-#endif
-
 #define SB_CELLS 256
 
 // The work unit (common.h): 128 x 16 luma + 2 x 64 x 8 chroma, two SBs side by
@@ -442,13 +438,6 @@ __device__ __forceinline__ void win_issue(WinLoad &W, const FrameCtx &f, __amdgp
       offc = cu + 16 * q2 + (pv ? uvd : 0) + __mul24((q3 * 171) >> 10, scd);  // q3 / 6, exact for q3 < 256
     }
     int off = 64 * i + 63 < WL_CH ? offl : (64 * i >= WL_CH ? offc : (q < WL_CH ? offl : offc));
-#if RECON_PROBE == 1  // timing probe: the same bytes as whole 128-B lines, 8 rows per load (wrong output)
-    off = (int)((ly & ~127) + (q >> 3) * f.sy + (q & 7) * 16);
-#elif RECON_PROBE == 2  // timing probe: no chroma window loads (wrong output)
-    if (64 * i >= WL_CH) continue;
-#elif RECON_PROBE == 4  // timing probe: every wave loads the same 6 KB (wrong output)
-    off = (int)(f.offy + 16 * q);
-#endif
     if (64 * i + 63 >= WL_CH + 2 * WC_CH && q >= WL_CH + 2 * WC_CH) continue;  // past the window
     W.v[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(ring, off, 0, 0));
   }
@@ -881,12 +870,8 @@ __device__ __forceinline__ void plan_pass(ReconLds &L, const FrameCtx &f, __amdg
   filter_all(L.win, K, f.bipred, x0, ty, tc, acc, mine, mine);
 }
 
-#ifndef RECON_RES_PREFETCH
-#define RECON_RES_PREFETCH 1
-#endif
-#ifndef RECON_WPE
-#define RECON_WPE 1
-#endif
+// 5 waves per SIMD (96 VGPRs; a few spills on the per-cell path only)
+#define RECON_WPE 5
 __global__ __launch_bounds__(64, RECON_WPE) void k_recon(const FrameBatch fb_, const ReconGeo g,
                                                            unsigned long long *__restrict__ dbg) {
   const FrameCtx *__restrict__ F = FRAME_BATCH_CTX();
@@ -994,7 +979,6 @@ __global__ __launch_bounds__(64, RECON_WPE) void k_recon(const FrameBatch fb_, c
       const __amdgpu_buffer_rsrc_t ring =
           __builtin_amdgcn_make_buffer_rsrc((void *)f.slots, 0, (int)f.ring_bytes, 0x00020000);
       const unsigned ma = doa ? pa.y : 0u, mb = dob ? pb.y : 0u;
-#if RECON_RES_PREFETCH
       if ((ma | mb) & (CELL_RES(0) | CELL_RES(1) | CELL_RES(2))) {
         // The unit's residual lines into L2 now, so the reads after the filter
         // hit there instead of waiting on HBM: one dword per 128-B line (luma
@@ -1013,7 +997,6 @@ __global__ __launch_bounds__(64, RECON_WPE) void k_recon(const FrameBatch fb_, c
         }
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rr, (lds_void *)(void *)L.mv0, 4, off, 0, 0, 0);
       }
-#endif
       const bool mine_a = cc < 16;  // filter lanes: columns of the left SB
       uint32_t ly[8], lc[4];
       {  // pass 0: mv0 (one window when both SBs share the key, else one per SB)
@@ -1098,9 +1081,6 @@ __global__ __launch_bounds__(64, RECON_WPE) void k_recon(const FrameBatch fb_, c
       const int offu = __builtin_amdgcn_readfirstlane((int)f.offu), offv = __builtin_amdgcn_readfirstlane((int)f.offv);
       const int oc = (pl1 ? offv : offu) + yc * f.sc + xcl;  // (a select of scalars, not a per-lane load of the field)
       typedef unsigned v4u __attribute__((ext_vector_type(4)));
-#if RECON_PROBE == 3  // timing probe: no pixel stores (wrong output)
-      if (f.W > 0) return;
-#endif
       const bool sty = (lane & 4) ? dob : doa, stc = (lane & 2) ? dob : doa;  // the lane's chunks' halves are ours
       if (sty) {
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, py0), cur, oy, 0, 0);
@@ -1119,9 +1099,6 @@ __global__ __launch_bounds__(64, RECON_WPE) void k_recon(const FrameBatch fb_, c
     }
   }
 
-#ifdef RECON_PLAN_ONLY
-  if (f.W > 0) return;
-#endif
   // reference lookup table (packed by the host)
   if (lane < 32) *(int *)&L.lut[4 * lane] = f.slot_lut[lane];
   if (stamp) {  // debug: the frame context's scalar loads have returned

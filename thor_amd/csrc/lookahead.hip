@@ -20,11 +20,6 @@
 #define LA_SIDE (2 * LA_RANGE + 1)
 #define LA_NCAND (LA_SIDE * LA_SIDE)  // 289
 #define LA_INL 8    // frame pairs that travel in the kernel arguments (24 bytes each)
-// tools/probes/lookahead_knock.hip times this kernel with one part removed (the results are then wrong):
-// 1 the source loads, 2 the 256-candidate pass of the search, 4 the butterflies across lanes.  0 in the library.
-#ifndef LA_KNOCK
-#define LA_KNOCK 0
-#endif
 // The tile's lowres pixels in LDS.  cur: one row above and four columns (one dword; only the last is a
 // neighbour) to the left of the tile; ref: LA_RANGE pixels all round, coordinates clamped to the plane.
 #define LA_CUR_COLS (8 * LA_TBW + 4)
@@ -54,7 +49,6 @@ static_assert(sizeof(LaArgs) <= 1024, "the pairs travel in the kernarg segment")
 // A group inside the plane takes four dword loads (two source rows x 8 bytes, any alignment); a group across
 // the plane's edge goes pixel by pixel.  Nothing is read outside source rows [0, 2 lh) and columns [0, 2 lw).
 __device__ __forceinline__ uint32_t la_lowres4(sse_gptr p, int stride, int x, int y, int lw, int lh) {
-  if (LA_KNOCK & 1) return (uint32_t)(x * 0x01010101 + y);
   const int yc = min(max(y, 0), lh - 1);
   const sse_gptr r0 = p + (long long)(2 * yc) * stride, r1 = r0 + stride;
   if (x >= 0 && x + 3 < lw) {
@@ -174,7 +168,7 @@ __global__ __launch_bounds__(256) void k_lookahead(const LaArgs A) {
       }
       // 256 candidates in one pass: lane 16 g + dx takes (dy, dx) for dy = 4 g .. 4 g + 3, so that the eleven
       // rows of the reference those four share are read and realigned once
-      if (!(LA_KNOCK & 2)) {
+      {
         const int dx = lane & 15, dy0 = (lane >> 4) * 4;
         const int rbase = (8 * by + dy0) * LA_REF_STRIDE + 8 * bx + dx;
         const uint32_t sh = (uint32_t)rbase & 3u;
@@ -249,12 +243,10 @@ __global__ __launch_bounds__(256) void k_lookahead(const LaArgs A) {
     const la_s2 o = __builtin_bit_cast(la_s2, (cw >> 8) & 0x00ff00ffu) - __builtin_bit_cast(la_s2, (pred >> 8) & 0x00ff00ffu);
     const la_s2 s1 = e + o, d1 = e - o;
     la_s2 ta = la_s2{(short)(s1.x + s1.y), (short)(s1.x - s1.y)}, tb = la_s2{(short)(d1.x + d1.y), (short)(d1.x - d1.y)};
-    if (!(LA_KNOCK & 4)) {
-      ta = la_butterfly<0>(ta, sg0), tb = la_butterfly<0>(tb, sg0);
-      ta = la_butterfly<1>(ta, sg1), tb = la_butterfly<1>(tb, sg1);
-      ta = la_butterfly<2>(ta, sg2), tb = la_butterfly<2>(tb, sg2);
-      ta = la_butterfly<3>(ta, sg3), tb = la_butterfly<3>(tb, sg3);
-    }
+    ta = la_butterfly<0>(ta, sg0), tb = la_butterfly<0>(tb, sg0);
+    ta = la_butterfly<1>(ta, sg1), tb = la_butterfly<1>(tb, sg1);
+    ta = la_butterfly<2>(ta, sg2), tb = la_butterfly<2>(tb, sg2);
+    ta = la_butterfly<3>(ta, sg3), tb = la_butterfly<3>(tb, sg3);
     // (a lane's four magnitudes sum to at most 4 * 16 320, a row's to at most 130 560)
     const uint32_t mag =
         (uint32_t)abs((int)ta.x) + (uint32_t)abs((int)ta.y) + (uint32_t)abs((int)tb.x) + (uint32_t)abs((int)tb.y);

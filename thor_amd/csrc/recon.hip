@@ -25,9 +25,7 @@ __device__ __forceinline__ void slow_mark(const FrameCtx &f, int sbx, int sby, i
 // PREP_CPW CUs per wave, 64 / PREP_CPW lanes each (round 6: 4 -- a 4K P frame is ~2 000 64x64 SKIP CUs
 // whose waves spent their short lives waiting on one descriptor load; a quarter as many waves, the four
 // descriptor loads of a wave in flight together)
-#ifndef PREP_CPW
 #define PREP_CPW 4
-#endif
 #define PREP_LPC (64 / PREP_CPW)
 __device__ __forceinline__ void prep_body(int bx, const FrameCtx &f) {
   const int b = (bx * 4 + (threadIdx.x >> 6)) * PREP_CPW + ((threadIdx.x & 63) / PREP_LPC);

@@ -6,7 +6,7 @@ bench clips, tests/golden/bench_clips.json), coded
   fetch : the same with the raw frames read from page-locked host memory by
           the launch itself (FETCH tasks)
 Each stream's .bit md5 is checked against the reference Thorenc's.
-Usage: python3 tools/seq_speed.py [K] [modes, comma separated; mode:KNOB=v sets THOR_SEQ_KNOB] [reps]"""
+Usage: python3 tools/seq_speed.py [K] [modes, comma separated] [reps]"""
 import hashlib
 import json
 import os
@@ -124,17 +124,10 @@ def run_seq(fetch, pre=0, nseq=None):
     bits = [b"".join(head[k] + [s.chunk(k, f) for f in range(nseq)] + tail[k]) for k in range(K)]
     # frames final per 100 ms
     marks = [(t, d) for t, d in tl if d in (1, K, K * nseq // 2, K * nseq)]
-    return bits, {"seq_ms": round(t_seq * 1e3, 1), "stats": st, "profile": s.profile, "env": {k: v for k, v in os.environ.items() if k.startswith("THOR_SEQ")}, "first_final_ms": round(first * 1e3, 1), "marks": marks[:8]}
+    return bits, {"seq_ms": round(t_seq * 1e3, 1), "stats": st, "profile": s.profile, "first_final_ms": round(first * 1e3, 1), "marks": marks[:8]}
 
 
-for spec in MODES:
-    # mode[:KNOB=v[:KNOB=v]]: THOR_SEQ_<KNOB> set for this mode's runs (read at each launch)
-    m, *kv = spec.split(":")
-    for k in [k for k in os.environ if k.startswith("THOR_SEQ_")]:
-        del os.environ[k]
-    for x in kv:
-        k, v = x.split("=")
-        os.environ["THOR_SEQ_" + k] = v
+for m in MODES:
     for r in range(REPS):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -146,7 +139,7 @@ for spec in MODES:
                                   int(parts[2]) if len(parts) > 2 else None)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        print(json.dumps({"mode": spec, "streams": K, "rep": r, "ms": round(dt * 1e3, 1),
+        print(json.dumps({"mode": m,"streams": K, "rep": r, "ms": round(dt * 1e3, 1),
                           "enc_mpx_s": round(K * nf * W * H / dt / 1e6, 1), "check": check(bits), "extra": extra}),
               flush=True)
 for e in encs:
