@@ -32,58 +32,13 @@ if ROOT not in sys.path:
 GOLD = os.path.join(ROOT, "tests", "golden")
 
 import lookahead_model as M  # noqa: E402
+from dev_frames import _luma, _side_context, dev  # noqa: E402, F401
 
 pytestmark = pytest.mark.gpu
 
 LA_INL = 8   # pairs per launch (thor_amd/csrc/lookahead.hip)
 GUARD = 64   # bytes either side of an output
 FILL = 0xA5
-
-
-class _Dev:
-    """Host arrays in device memory for the life of a test."""
-
-    def __init__(self):
-        from thor_amd import lib as L
-
-        self.L, self.lib, self.ptrs = L, L.load(), []
-
-    def put(self, arr):
-        a = np.ascontiguousarray(arr)
-        p = self.lib.thor_dev_alloc(max(a.nbytes, 16))
-        assert p
-        self.ptrs.append(p)
-        self.L.check(self.lib.thor_h2d(p, a.ctypes.data, a.nbytes), "thor_h2d")
-        return p
-
-    def get(self, p, nbytes):
-        out = np.empty(nbytes, np.uint8)
-        self.L.check(self.lib.thor_d2h(out.ctypes.data, p, nbytes), "thor_d2h")
-        return out
-
-    def free(self):
-        for p in self.ptrs:
-            self.lib.thor_dev_free(p)
-        self.ptrs = []
-
-
-@pytest.fixture()
-def dev():
-    d = _Dev()
-    yield d
-    d.free()
-
-
-def _luma(dev, plane, stride, off):
-    """A luma plane laid out with `stride`, its first pixel `off` bytes past an allocation's start; the bytes
-    around the pixels are noise, so a kernel that reads past a row is caught.  No chroma: only luma is read."""
-    from thor_amd import lib as L
-
-    h, w = plane.shape
-    assert stride >= w
-    buf = np.random.default_rng(stride * 7 + off).integers(0, 256, off + h * stride + 16, dtype=np.uint8)
-    buf[off:off + h * stride].reshape(h, stride)[:, :w] = plane
-    return L.ThorYuvPlanes(dev.put(buf) + off, None, None, stride, 0)
 
 
 def _enqueue(dev, cur, ref, w, h, blocks=True, stream=None):
@@ -207,16 +162,6 @@ def test_lookahead_synthetic_scene_cut(dev):
         assert (recs[k] == want[k][0]).all(), k
     for percent in (70, 80, 90):
         assert lookahead.scene_cuts(sums, percent) == [0, 3]
-
-
-def _side_context():
-    """A decoder context, for its stream (no torch in this process: torch's HIP runtime has to come up before
-    the library's)."""
-    from thor_amd.bitstream import parse_stream
-    from thor_amd.decoder import GpuDecoder
-
-    with open(os.path.join(GOLD, "cif_low.bit"), "rb") as f:
-        return GpuDecoder(parse_stream(f.read())[0])
 
 
 @pytest.mark.parametrize("blocks", [True, False])

@@ -26,6 +26,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 GOLD = os.path.join(ROOT, "tests", "golden")
 
+from dev_frames import _frame, _random_planes, dev  # noqa: E402, F401
+
 pytestmark = pytest.mark.gpu
 
 with open(os.path.join(GOLD, "quality.json")) as _f:
@@ -62,57 +64,6 @@ def _bounded_waits():
 
 
 # ---- the primitive ---------------------------------------------------------------------------------------------
-class _Dev:
-    """Host arrays in device memory for the life of a test."""
-
-    def __init__(self):
-        from thor_amd import lib as L
-
-        self.L, self.lib, self.ptrs = L, L.load(), []
-
-    def put(self, arr):
-        a = np.ascontiguousarray(arr)
-        p = self.lib.thor_dev_alloc(max(a.nbytes, 16))
-        assert p
-        self.ptrs.append(p)
-        self.L.check(self.lib.thor_h2d(p, a.ctypes.data, a.nbytes), "thor_h2d")
-        return p
-
-    def free(self):
-        for p in self.ptrs:
-            self.lib.thor_dev_free(p)
-        self.ptrs = []
-
-
-@pytest.fixture()
-def dev():
-    d = _Dev()
-    yield d
-    d.free()
-
-
-def _frame(dev, planes, sy, sc, off):
-    """The three planes (2-D uint8) laid out with strides sy / sc, the first pixel of each `off` bytes past a
-    256-byte boundary; the bytes around the pixels are noise, so a kernel that reads past a row is caught."""
-    from thor_amd import lib as L
-
-    rng = np.random.default_rng(sy * 7 + sc * 3 + off)
-    ptrs = []
-    for p, s in zip(planes, (sy, sc, sc)):
-        h, w = p.shape
-        assert s >= w
-        buf = rng.integers(0, 256, off + h * s + 16, dtype=np.uint8)
-        view = buf[off:off + h * s].reshape(h, s)
-        view[:, :w] = p
-        ptrs.append(dev.put(buf) + off)
-    return L.ThorYuvPlanes(ptrs[0], ptrs[1], ptrs[2], sy, sc)
-
-
-def _random_planes(w, h, seed):
-    rng = np.random.default_rng(seed)
-    return [rng.integers(0, 256, (ph, pw), dtype=np.uint8) for pw, ph in ((w, h), (w // 2, h // 2), (w // 2, h // 2))]
-
-
 def _np_sse(a, b):
     return [int(((x.astype(np.int64) - y.astype(np.int64)) ** 2).sum()) for x, y in zip(a, b)]
 

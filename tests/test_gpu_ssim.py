@@ -33,70 +33,11 @@ if ROOT not in sys.path:
 GOLD = os.path.join(ROOT, "tests", "golden")
 
 import ssim_model as M  # noqa: E402
+from dev_frames import _dims, _frame, _random_planes, _side_context, dev  # noqa: E402, F401
 
 pytestmark = pytest.mark.gpu
 
 SSIM_INL = 8  # pairs per launch (thor_amd/csrc/ssim.hip)
-
-
-class _Dev:
-    """Host arrays in device memory for the life of a test."""
-
-    def __init__(self):
-        from thor_amd import lib as L
-
-        self.L, self.lib, self.ptrs = L, L.load(), []
-
-    def put(self, arr):
-        a = np.ascontiguousarray(arr)
-        p = self.lib.thor_dev_alloc(max(a.nbytes, 16))
-        assert p
-        self.ptrs.append(p)
-        self.L.check(self.lib.thor_h2d(p, a.ctypes.data, a.nbytes), "thor_h2d")
-        return p
-
-    def get(self, p, nbytes):
-        out = np.empty(nbytes, np.uint8)
-        self.L.check(self.lib.thor_d2h(out.ctypes.data, p, nbytes), "thor_d2h")
-        return out
-
-    def free(self):
-        for p in self.ptrs:
-            self.lib.thor_dev_free(p)
-        self.ptrs = []
-
-
-@pytest.fixture()
-def dev():
-    d = _Dev()
-    yield d
-    d.free()
-
-
-def _frame(dev, planes, sy, sc, off):
-    """The three planes (2-D uint8) laid out with strides sy / sc, the first pixel of each `off` bytes past a
-    256-byte boundary; the bytes around the pixels are noise, so a kernel that reads past a row is caught."""
-    from thor_amd import lib as L
-
-    rng = np.random.default_rng(sy * 7 + sc * 3 + off)
-    ptrs = []
-    for p, s in zip(planes, (sy, sc, sc)):
-        h, w = p.shape
-        assert s >= w
-        buf = rng.integers(0, 256, off + h * s + 16, dtype=np.uint8)
-        view = buf[off:off + h * s].reshape(h, s)
-        view[:, :w] = p
-        ptrs.append(dev.put(buf) + off)
-    return L.ThorYuvPlanes(ptrs[0], ptrs[1], ptrs[2], sy, sc)
-
-
-def _dims(w, h):
-    return ((w, h), (w // 2, h // 2), (w // 2, h // 2))
-
-
-def _random_planes(w, h, seed):
-    rng = np.random.default_rng(seed)
-    return [rng.integers(0, 256, (ph, pw), dtype=np.uint8) for pw, ph in _dims(w, h)]
 
 
 CONTENT = ["random", "noise", "identical", "inverted", "constant", "step"]
@@ -186,16 +127,6 @@ def test_ssim_ignores_the_remainder_pixels(dev):
     got = ssim_i420([_frame(dev, a, w + 3, w // 2 + 5, 1), _frame(dev, a2, w + 3, w // 2 + 5, 1)],
                     [_frame(dev, b, w, w // 2, 0), _frame(dev, b2, w, w // 2, 0)], w, h).tolist()
     assert got[0] == got[1] == M.frame_sums(a, b)
-
-
-def _side_context():
-    """A decoder context, for its stream (no torch in this process: torch's HIP runtime has to come up before
-    the library's)."""
-    from thor_amd.bitstream import parse_stream
-    from thor_amd.decoder import GpuDecoder
-
-    with open(os.path.join(GOLD, "cif_low.bit"), "rb") as f:
-        return GpuDecoder(parse_stream(f.read())[0])
 
 
 @pytest.mark.parametrize("stream", ["null", "own"])

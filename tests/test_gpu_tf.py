@@ -33,63 +33,13 @@ if ROOT not in sys.path:
 GOLD = os.path.join(ROOT, "tests", "golden")
 
 import tf_model as M  # noqa: E402
+from dev_frames import _frame_in, _side_context, dev  # noqa: E402, F401
 
 pytestmark = pytest.mark.gpu
 
 TF_INL = 4   # targets per launch (thor_amd/csrc/tf.hip)
 GUARD = 64   # bytes either side of an output
 FILL = 0xA5
-
-
-class _Dev:
-    """Host arrays in device memory for the life of a test."""
-
-    def __init__(self):
-        from thor_amd import lib as L
-
-        self.L, self.lib, self.ptrs = L, L.load(), []
-
-    def put(self, arr):
-        a = np.ascontiguousarray(arr)
-        p = self.lib.thor_dev_alloc(max(a.nbytes, 16))
-        assert p
-        self.ptrs.append(p)
-        self.L.check(self.lib.thor_h2d(p, a.ctypes.data, a.nbytes), "thor_h2d")
-        return p
-
-    def get(self, p, nbytes):
-        out = np.empty(nbytes, np.uint8)
-        self.L.check(self.lib.thor_d2h(out.ctypes.data, p, nbytes), "thor_d2h")
-        return out
-
-    def free(self):
-        for p in self.ptrs:
-            self.lib.thor_dev_free(p)
-        self.ptrs = []
-
-
-@pytest.fixture()
-def dev():
-    d = _Dev()
-    yield d
-    d.free()
-
-
-def _plane_in(dev, plane, stride, off):
-    """A plane laid out with `stride`, its first pixel `off` bytes past an allocation's start; the bytes around
-    the pixels are noise, so a kernel that reads past a row is caught."""
-    h, w = plane.shape
-    assert stride >= w
-    buf = np.random.default_rng(stride * 7 + off + h).integers(0, 256, off + h * stride + 16, dtype=np.uint8)
-    buf[off:off + h * stride].reshape(h, stride)[:, :w] = plane
-    return dev.put(buf) + off
-
-
-def _frame_in(dev, planes, pad, off):
-    """ThorYuvPlanes of a (y, u, v) triple: strides width + pad (chroma: its own width + pad), offset `off`."""
-    y, u, v = planes
-    sy, sc = y.shape[1] + pad, u.shape[1] + pad
-    return dev.L.ThorYuvPlanes(_plane_in(dev, y, sy, off), _plane_in(dev, u, sc, off), _plane_in(dev, v, sc, off), sy, sc)
 
 
 class _Out:
@@ -307,16 +257,6 @@ def test_filter_sequence_against_model(dev, radius):
         assert (got[k] == want[k]).all(), (radius, k)
     assert (dev.get(d_src, seq.size).reshape(n, -1) == seq).all()
     assert (want != seq).any()
-
-
-def _side_context():
-    """A decoder context, for its stream (no torch in this process: torch's HIP runtime has to come up before
-    the library's)."""
-    from thor_amd.bitstream import parse_stream
-    from thor_amd.decoder import GpuDecoder
-
-    with open(os.path.join(GOLD, "cif_low.bit"), "rb") as f:
-        return GpuDecoder(parse_stream(f.read())[0])
 
 
 def test_tf_behind_the_scaler_on_one_stream(dev):

@@ -42,7 +42,7 @@ def test_constants():
 
 
 def _load4_in_plane(x, y, w, h):
-    """tf_load4: row clamped; bytes x .. x + 3 of a group inside the plane, else clamped pixels."""
+    """ld4_clamped (frame_ops.h): row clamped; bytes x .. x + 3 of a group inside the plane, else clamped pixels."""
     yc = np.clip(y, 0, h - 1)
     fast = (x >= 0) & (x + 3 < w)
     lo = np.where(fast, x, np.clip(x, 0, w - 1))

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "common.h"
+#include "frame_ops.h"  // slot_planes
 
 // kernels (intra.hip, inter.hip, loopfilter.hip): the frame batch by value, first argument
 __global__ void k_frame_prep(const FrameBatch);
@@ -507,11 +508,6 @@ static int recon_lds_pad() {
     return e ? atoi(e) : 0;
   }();
   return v;
-}
-
-static thor_yuv_planes_t slot_planes(const thor_dec *d, int s) {
-  uint8_t *base = d->slots + (long long)s * d->slot_bytes;
-  return thor_yuv_planes_t{base + d->offy, base + d->offu, base + d->offv, d->sy, d->sc};
 }
 
 // The frames' temporal-interpolated references (interpolate_frames + pad_yuv_frame,

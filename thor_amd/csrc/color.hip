@@ -9,8 +9,8 @@
 // template parameters, the frame is grid dimension z.  A lane owns a strip two
 // rows high and 8 pixels wide, so both rows share one chroma fetch; a wave
 // reads and writes contiguous row segments (64 strips = 512 pixels).
-// (unity build: follows quality.hip in libthor_amd.hip)
-#include "common.h"
+// The decoder context, find_slot_host and HIPCHK are capi.hip's.
+#include "frame_ops.h"
 
 #define CSC_INL THOR_CSC_LAUNCH_IMAGES  // images that travel in the kernel arguments (56 bytes each)
 
@@ -42,26 +42,8 @@ static const int32_t CSC_INV[4][9] = {{19077, 0, 26149, 19077, -6419, -13320, 19
                                       {19077, 0, 29372, 19077, -3494, -8731, 19077, 34610, 0},
                                       {16384, 0, 25802, 16384, -3069, -7670, 16384, 30402, 0}};
 
-// The images are in global memory: accesses through pointers of that address space are global_*
-// (quality.hip), which take any alignment -- also in their 8- and 16-byte forms, so one instruction per
-// row segment serves aligned and unaligned images alike (the memory pipeline splits what straddles).
-// Every address is a uniform row base plus the lane's unsigned offset (SGPR base + 32-bit VGPR offset).
-typedef __attribute__((address_space(1))) uint8_t *csc_gp;
-typedef const __attribute__((address_space(1))) uint8_t *csc_cgp;
-typedef __attribute__((address_space(1))) float *csc_gpf;
-typedef const __attribute__((address_space(1))) float *csc_cgpf;
-typedef uint32_t __attribute__((aligned(1))) csc_u32u;
-typedef uint32_t csc_v2 __attribute__((ext_vector_type(2)));
-typedef csc_v2 __attribute__((aligned(1))) csc_v2u;
-typedef float csc_f4 __attribute__((ext_vector_type(4)));
-typedef csc_f4 __attribute__((aligned(4))) csc_f4u;  // (float images are 4-byte aligned: include/thor_amd.h)
-
-__device__ __forceinline__ uint32_t csc_ld4(csc_cgp p) { return *(const __attribute__((address_space(1))) csc_u32u *)p; }
-__device__ __forceinline__ void csc_st4(csc_gp p, uint32_t v) { *(__attribute__((address_space(1))) csc_u32u *)p = v; }
-__device__ __forceinline__ csc_v2 csc_ld8(csc_cgp p) { return *(const __attribute__((address_space(1))) csc_v2u *)p; }
-__device__ __forceinline__ void csc_st8(csc_gp p, csc_v2 v) { *(__attribute__((address_space(1))) csc_v2u *)p = v; }
-__device__ __forceinline__ csc_f4 csc_ld16f(csc_cgpf p) { return *(const __attribute__((address_space(1))) csc_f4u *)p; }
-__device__ __forceinline__ void csc_st16f(csc_gpf p, csc_f4 v) { *(__attribute__((address_space(1))) csc_f4u *)p = v; }
+// Every global address (frame_ops.h) is a uniform row base plus the lane's unsigned offset (SGPR base + 32-bit
+// VGPR offset).
 __device__ __forceinline__ int csc_byte(uint32_t v, int k) { return (int)((v >> (8 * k)) & 255u); }
 // clamp to [0, 255].  The empty asm hides the result's origin from the instruction selector: it would
 // otherwise fuse shift, clamp and the packing of two such bytes into v_ashr_pk_u8_i32 and or the other two
@@ -99,20 +81,20 @@ __device__ __forceinline__ int csc_chroma(const int *k, int row, int rs, int gs,
 // One pixel of an RGB image (frames narrower than a strip take this path, a lane per 2x2 block).
 template <int FMT>
 __device__ __forceinline__ void csc_put_px(const CscImg &P, int x, int y, const int px[3]) {
-  const csc_gp row = (csc_gp)P.rgb + (long long)y * P.rs;
+  const gptr row = (gptr)P.rgb + (long long)y * P.rs;
   for (int c = 0; c < 3; c++) {
     if (FMT == THOR_RGB8_PACKED) row[(unsigned)(3 * x + c)] = (uint8_t)px[c];
     else if (FMT == THOR_RGB8_PLANAR) (row + c * P.ps)[(unsigned)x] = (uint8_t)px[c];
-    else ((csc_gpf)(row + c * P.ps))[(unsigned)x] = csc_unorm(px[c]);
+    else ((gptrf)(row + c * P.ps))[(unsigned)x] = csc_unorm(px[c]);
   }
 }
 template <int FMT>
 __device__ __forceinline__ void csc_get_px(const CscImg &P, int x, int y, int px[3]) {
-  const csc_cgp row = (csc_cgp)P.rgb + (long long)y * P.rs;
+  const gcptr row = (gcptr)P.rgb + (long long)y * P.rs;
   for (int c = 0; c < 3; c++) {
     if (FMT == THOR_RGB8_PACKED) px[c] = row[(unsigned)(3 * x + c)];
     else if (FMT == THOR_RGB8_PLANAR) px[c] = (row + c * P.ps)[(unsigned)x];
-    else px[c] = csc_quant(((csc_cgpf)(row + c * P.ps))[(unsigned)x]);
+    else px[c] = csc_quant(((gcptrf)(row + c * P.ps))[(unsigned)x]);
   }
 }
 
@@ -120,8 +102,8 @@ __device__ __forceinline__ void csc_get_px(const CscImg &P, int x, int y, int px
 // c[5] = right neighbour, the neighbours clamped to [0, CW - 1]: a second and third load that hit the
 // cache lines the adjacent lanes fetch.
 template <int BILIN>
-__device__ __forceinline__ void csc_chroma_row(csc_cgp row, int cx0, int CW, int c[6]) {
-  const uint32_t d = csc_ld4(row + (unsigned)cx0);
+__device__ __forceinline__ void csc_chroma_row(gcptr row, int cx0, int CW, int c[6]) {
+  const uint32_t d = g_ld4(row + (unsigned)cx0);
 #pragma unroll
   for (int j = 0; j < 4; j++) c[1 + j] = csc_byte(d, j);
   if (BILIN) {
@@ -150,8 +132,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
   const int cy = blockIdx.y * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (uniform: SGPRs)
   const int strip = blockIdx.x * 64 + (threadIdx.x & 63);
   if (cy >= CH) return;
-  const csc_cgp Y = (csc_cgp)P.y + (long long)(2 * cy) * P.sy;
-  const csc_cgp U = (csc_cgp)P.u + (long long)cy * P.sc, V = (csc_cgp)P.v + (long long)cy * P.sc;
+  const gcptr Y = (gcptr)P.y + (long long)(2 * cy) * P.sy;
+  const gcptr U = (gcptr)P.u + (long long)cy * P.sc, V = (gcptr)P.v + (long long)cy * P.sc;
   if (W < 8) {  // (uniform) narrower than a strip: a lane per 2x2 block, sample by sample
     const int bx = strip;
     if (bx >= CW) return;
@@ -160,7 +142,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         int u16 = 16 * U[(unsigned)bx], v16 = 16 * V[(unsigned)bx];
         if (BILIN) {
           const int nx = dx ? min(bx + 1, CW - 1) : max(bx - 1, 0), ny = r ? min(cy + 1, CH - 1) : max(cy - 1, 0);
-          const csc_cgp Un = (csc_cgp)P.u + (long long)ny * P.sc, Vn = (csc_cgp)P.v + (long long)ny * P.sc;
+          const gcptr Un = (gcptr)P.u + (long long)ny * P.sc, Vn = (gcptr)P.v + (long long)ny * P.sc;
           u16 = 9 * U[(unsigned)bx] + 3 * U[(unsigned)nx] + 3 * Un[(unsigned)bx] + Un[(unsigned)nx];
           v16 = 9 * V[(unsigned)bx] + 3 * V[(unsigned)nx] + 3 * Vn[(unsigned)bx] + Vn[(unsigned)nx];
         }
@@ -173,7 +155,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
   if (strip * 8 >= W) return;
   const int x0 = min(strip * 8, W - 8), cx0 = x0 >> 1;
 
-  const csc_v2 yr[2] = {csc_ld8(Y + (unsigned)x0), csc_ld8(Y + P.sy + (unsigned)x0)};
+  const u32x2 yr[2] = {g_ld8(Y + (unsigned)x0), g_ld8(Y + P.sy + (unsigned)x0)};
   // chroma: the strip's row, and for bilinear the rows above and below it (clamped at the frame edge)
   int cu[6], cv[6];
   csc_chroma_row<BILIN>(U, cx0, CW, cu);
@@ -184,12 +166,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     if (BILIN) {
       const int ny = r ? min(cy + 1, CH - 1) : max(cy - 1, 0);
       int nu[6], nv[6], h[8], g[8];
-      csc_chroma_row<1>((csc_cgp)P.u + (long long)ny * P.sc, cx0, CW, nu);
+      csc_chroma_row<1>((gcptr)P.u + (long long)ny * P.sc, cx0, CW, nu);
       csc_chroma_h(cu, h);
       csc_chroma_h(nu, g);
 #pragma unroll
       for (int i = 0; i < 8; i++) u16[i] = 3 * h[i] + g[i];
-      csc_chroma_row<1>((csc_cgp)P.v + (long long)ny * P.sc, cx0, CW, nv);
+      csc_chroma_row<1>((gcptr)P.v + (long long)ny * P.sc, cx0, CW, nv);
       csc_chroma_h(cv, h);
       csc_chroma_h(nv, g);
 #pragma unroll
@@ -201,7 +183,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     int yv[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) yv[i] = csc_byte(i < 4 ? yr[r].x : yr[r].y, i & 3);
-    const csc_gp row = (csc_gp)P.rgb + (long long)(2 * cy + r) * P.rs;
+    const gptr row = (gptr)P.rgb + (long long)(2 * cy + r) * P.rs;
     if (FMT == THOR_RGB8_PACKED) {  // 24 contiguous bytes: a wave writes 1 536 contiguous bytes per row
       int px[3][8];
 #pragma unroll
@@ -216,18 +198,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         for (int t = 0; t < 4; t++) b[t] = px[(4 * j + t) % 3][(4 * j + t) / 3];
         d[j] = csc_pack4(b[0], b[1], b[2], b[3]);
       }
-      const csc_gp o = row + (unsigned)(x0 * 3);
-      csc_st8(o, csc_v2{d[0], d[1]});
-      csc_st8(o + 8, csc_v2{d[2], d[3]});
-      csc_st8(o + 16, csc_v2{d[4], d[5]});
+      const gptr o = row + (unsigned)(x0 * 3);
+      g_st8(o, u32x2{d[0], d[1]});
+      g_st8(o + 8, u32x2{d[2], d[3]});
+      g_st8(o + 16, u32x2{d[4], d[5]});
     } else if (FMT == THOR_RGB8_PLANAR) {
 #pragma unroll
       for (int c = 0; c < 3; c++) {  // a plane at a time
         int px[8];
 #pragma unroll
         for (int i = 0; i < 8; i++) px[i] = csc_rgb(A.k, c, yv[i], u16[i], v16[i]);
-        csc_st8(row + c * P.ps + (unsigned)x0,
-                csc_v2{csc_pack4(px[0], px[1], px[2], px[3]), csc_pack4(px[4], px[5], px[6], px[7])});
+        g_st8(row + c * P.ps + (unsigned)x0,
+                u32x2{csc_pack4(px[0], px[1], px[2], px[3]), csc_pack4(px[4], px[5], px[6], px[7])});
       }
     } else {
 #pragma unroll
@@ -235,9 +217,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         int px[8];
 #pragma unroll
         for (int i = 0; i < 8; i++) px[i] = csc_rgb(A.k, c, yv[i], u16[i], v16[i]);
-        const csc_gpf o = (csc_gpf)(row + c * P.ps) + (unsigned)x0;
-        csc_st16f(o, csc_f4{csc_unorm(px[0]), csc_unorm(px[1]), csc_unorm(px[2]), csc_unorm(px[3])});
-        csc_st16f(o + 4, csc_f4{csc_unorm(px[4]), csc_unorm(px[5]), csc_unorm(px[6]), csc_unorm(px[7])});
+        const gptrf o = (gptrf)(row + c * P.ps) + (unsigned)x0;
+        g_st16f(o, f32x4{csc_unorm(px[0]), csc_unorm(px[1]), csc_unorm(px[2]), csc_unorm(px[3])});
+        g_st16f(o + 4, f32x4{csc_unorm(px[4]), csc_unorm(px[5]), csc_unorm(px[6]), csc_unorm(px[7])});
       }
     }
   }
@@ -251,7 +233,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
   const int cy = blockIdx.y * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int strip = blockIdx.x * 64 + (threadIdx.x & 63);
   if (cy >= CH) return;
-  const csc_gp U = (csc_gp)P.u + (long long)cy * P.sc, V = (csc_gp)P.v + (long long)cy * P.sc;
+  const gptr U = (gptr)P.u + (long long)cy * P.sc, V = (gptr)P.v + (long long)cy * P.sc;
   if (W < 8) {  // (uniform) a lane per 2x2 block
     const int bx = strip;
     if (bx >= CW) return;
@@ -260,7 +242,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
       for (int dx = 0; dx < 2; dx++) {
         int px[3];
         csc_get_px<FMT>(P, 2 * bx + dx, 2 * cy + r, px);
-        ((csc_gp)P.y + (long long)(2 * cy + r) * P.sy)[(unsigned)(2 * bx + dx)] = (uint8_t)csc_luma(A.k, px[0], px[1], px[2]);
+        ((gptr)P.y + (long long)(2 * cy + r) * P.sy)[(unsigned)(2 * bx + dx)] = (uint8_t)csc_luma(A.k, px[0], px[1], px[2]);
         for (int c = 0; c < 3; c++) sum[c] += px[c];
       }
     U[(unsigned)bx] = (uint8_t)csc_chroma(A.k, 1, sum[0], sum[1], sum[2]);
@@ -274,25 +256,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 #pragma unroll
   for (int r = 0; r < 2; r++) {
     int px[3][8];
-    const csc_cgp row = (csc_cgp)P.rgb + (long long)(2 * cy + r) * P.rs;
+    const gcptr row = (gcptr)P.rgb + (long long)(2 * cy + r) * P.rs;
     if (FMT == THOR_RGB8_PACKED) {
-      const csc_cgp s = row + (unsigned)(x0 * 3);
-      const csc_v2 a = csc_ld8(s), b = csc_ld8(s + 8), c = csc_ld8(s + 16);
+      const gcptr s = row + (unsigned)(x0 * 3);
+      const u32x2 a = g_ld8(s), b = g_ld8(s + 8), c = g_ld8(s + 16);
       const uint32_t d[6] = {a.x, a.y, b.x, b.y, c.x, c.y};
 #pragma unroll
       for (int j = 0; j < 24; j++) px[j % 3][j / 3] = csc_byte(d[j >> 2], j & 3);
     } else if (FMT == THOR_RGB8_PLANAR) {
 #pragma unroll
       for (int c = 0; c < 3; c++) {
-        const csc_v2 d = csc_ld8(row + c * P.ps + (unsigned)x0);
+        const u32x2 d = g_ld8(row + c * P.ps + (unsigned)x0);
 #pragma unroll
         for (int i = 0; i < 8; i++) px[c][i] = csc_byte(i < 4 ? d.x : d.y, i & 3);
       }
     } else {
 #pragma unroll
       for (int c = 0; c < 3; c++) {
-        const csc_cgpf s = (csc_cgpf)(row + c * P.ps) + (unsigned)x0;
-        const csc_f4 a = csc_ld16f(s), b = csc_ld16f(s + 4);
+        const gcptrf s = (gcptrf)(row + c * P.ps) + (unsigned)x0;
+        const f32x4 a = g_ld16f(s), b = g_ld16f(s + 4);
         px[c][0] = csc_quant(a.x), px[c][1] = csc_quant(a.y), px[c][2] = csc_quant(a.z), px[c][3] = csc_quant(a.w);
         px[c][4] = csc_quant(b.x), px[c][5] = csc_quant(b.y), px[c][6] = csc_quant(b.z), px[c][7] = csc_quant(b.w);
       }
@@ -300,8 +282,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     int yv[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) yv[i] = csc_luma(A.k, px[0][i], px[1][i], px[2][i]);
-    csc_st8((csc_gp)P.y + (long long)(2 * cy + r) * P.sy + (unsigned)x0,
-            csc_v2{csc_pack4(yv[0], yv[1], yv[2], yv[3]), csc_pack4(yv[4], yv[5], yv[6], yv[7])});
+    g_st8((gptr)P.y + (long long)(2 * cy + r) * P.sy + (unsigned)x0,
+            u32x2{csc_pack4(yv[0], yv[1], yv[2], yv[3]), csc_pack4(yv[4], yv[5], yv[6], yv[7])});
 #pragma unroll
     for (int c = 0; c < 3; c++)
 #pragma unroll
@@ -313,8 +295,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     cb[j] = csc_chroma(A.k, 1, sum[0][j], sum[1][j], sum[2][j]);
     cr[j] = csc_chroma(A.k, 2, sum[0][j], sum[1][j], sum[2][j]);
   }
-  csc_st4(U + (unsigned)cx0, csc_pack4(cb[0], cb[1], cb[2], cb[3]));
-  csc_st4(V + (unsigned)cx0, csc_pack4(cr[0], cr[1], cr[2], cr[3]));
+  g_st4(U + (unsigned)cx0, csc_pack4(cb[0], cb[1], cb[2], cb[3]));
+  g_st4(V + (unsigned)cx0, csc_pack4(cr[0], cr[1], cr[2], cr[3]));
 }
 
 // Everything that can be refused without a device: THOR_OK or THOR_ERR_ARG.
@@ -328,8 +310,7 @@ static int csc_check(const thor_yuv_planes_t *yuv, const thor_image_t *img, int 
   if (fmt != THOR_RGB8_PACKED && fmt != THOR_RGB8_PLANAR && fmt != THOR_RGBF32_PLANAR) return THOR_ERR_ARG;
   const long long row = fmt == THOR_RGB8_PACKED ? 3LL * W : fmt == THOR_RGB8_PLANAR ? (long long)W : 4LL * W;
   for (int i = 0; i < n; i++) {
-    if (!yuv[i].y || !yuv[i].u || !yuv[i].v || !img[i].data || img[i].format != fmt) return THOR_ERR_ARG;
-    if (yuv[i].stride_y < W || yuv[i].stride_c < (W >> 1) || img[i].stride < row) return THOR_ERR_ARG;
+    if (!planes_ok(yuv[i], W) || !img[i].data || img[i].format != fmt || img[i].stride < row) return THOR_ERR_ARG;
     if (fmt == THOR_RGBF32_PLANAR &&
         (((uintptr_t)img[i].data | (uintptr_t)(unsigned)img[i].stride | (uintptr_t)img[i].plane_stride) & 3))
       return THOR_ERR_ARG;
@@ -368,8 +349,7 @@ static int csc_enqueue(const thor_yuv_planes_t *yuv, const thor_image_t *img, in
   }
   const int fmt = img[0].format;
   const unsigned gx = (unsigned)((W + 511) / 512), gy = (unsigned)(((H >> 1) + 3) / 4);
-  for (int i0 = 0; i0 < n; i0 += CSC_INL) {
-    const int m = n - i0 < CSC_INL ? n - i0 : CSC_INL;
+  return launch_batches(n, CSC_INL, [&](int i0, int m) {
     for (int i = 0; i < m; i++) {
       const thor_yuv_planes_t &y = yuv[i0 + i];
       const thor_image_t &r = img[i0 + i];
@@ -386,9 +366,7 @@ static int csc_enqueue(const thor_yuv_planes_t *yuv, const thor_image_t *img, in
       else if (fmt == THOR_RGB8_PLANAR) k_csc_from_rgb<THOR_RGB8_PLANAR><<<g, 256, 0, st>>>(A);
       else k_csc_from_rgb<THOR_RGBF32_PLANAR><<<g, 256, 0, st>>>(A);
     }
-  }
-  if (hipGetLastError() != hipSuccess) return THOR_ERR_HIP;
-  return THOR_OK;
+  });
 }
 
 extern "C" {
@@ -419,8 +397,7 @@ int thor_dec_frame_planes(thor_dec_t *d, int frame_num, thor_yuv_planes_t *out) 
   if (!d || !out) return THOR_ERR_ARG;
   const int s = find_slot_host(d, frame_num);
   if (s < 0) return THOR_ERR_REF;
-  uint8_t *base = d->slots + (long long)s * d->slot_bytes;
-  *out = thor_yuv_planes_t{base + d->offy, base + d->offu, base + d->offv, d->sy, d->sc};
+  *out = slot_planes(d, s);
   return THOR_OK;
 }
 

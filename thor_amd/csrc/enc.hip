@@ -25,6 +25,12 @@
 #include "common.h"
 #include "enc_gop.h"
 #include "enc_rd.h"
+#include "frame_ops.h"  // SsePair, sse_fill_pair, slot_planes
+
+// the frame utilities' launches the encoder enqueues on its own streams
+static int sse_enqueue(const SsePair *dev, const SsePair *host, int n, int W, int H, unsigned long long *sse,
+                       hipStream_t st);  // quality.hip
+static int ssim_enqueue(const SsePair *host, int n, int W, int H, unsigned long long *sums, hipStream_t st);  // ssim.hip
 
 #include <deque>
 #include <map>
@@ -1024,11 +1030,6 @@ static int enc_prepare(thor_enc *e, const uint8_t *orig, int orig_stride, TeJob 
   return THOR_OK;  // the cells, SB dependency counters and queue are set up by k_enc_clear (one launch for the batch)
 }
 
-static thor_yuv_planes_t enc_slot_planes(const thor_enc *e, int slot) {
-  uint8_t *b = e->slots + (long long)slot * e->slot_bytes;
-  return thor_yuv_planes_t{b + e->offy, b + e->offu, b + e->offv, e->sy, e->sc};
-}
-
 // The frame's interpolated reference into the interpolation slot, on the
 // context's stream: interpolate_frames + pad_yuv_frame (enc/mainenc.c:328-330,
 // :385-387), the decoder's kernels (tme.hip, k_pad).
@@ -1037,8 +1038,8 @@ static int enc_interp(thor_enc *e, const TeFramePlan &pl) {
   if (!e->ti || e->islot < 0 || a < 0 || a >= 33 || b < 0 || b >= 33 || e->slot_of_window[a] < 0 ||
       e->slot_of_window[b] < 0)
     return THOR_ERR_REF;
-  const thor_yuv_planes_t ra = enc_slot_planes(e, e->slot_of_window[a]), rb = enc_slot_planes(e, e->slot_of_window[b]);
-  const thor_yuv_planes_t o = enc_slot_planes(e, e->islot);
+  const thor_yuv_planes_t ra = slot_planes(e, e->slot_of_window[a]), rb = slot_planes(e, e->slot_of_window[b]);
+  const thor_yuv_planes_t o = slot_planes(e, e->islot);
   const int rc = thor_interpolate_frames(e->ti, &ra, &rb, THOR_PAD_Y, &o, pl.interp_ratio, pl.interp_pos, e->stream);
   if (rc != THOR_OK) return rc;
   FrameBatch fb;
@@ -1488,10 +1489,8 @@ int thor_enc_recon_ssim(thor_enc_t *e, const thor_yuv_planes_t *orig, int64_t *s
   for (const EncPool::Pending &q : P.pending)
     for (thor_enc *x : q.es)
       if (x == e) return THOR_ERR_ARG;
-  uint8_t *b = e->slots + (long long)e->last_slot * e->slot_bytes;
-  const thor_yuv_planes_t rec = {b + e->offy, b + e->offu, b + e->offv, e->sy, e->sc};
   SsePair pr;
-  if (!sse_fill_pair(pr, *orig, rec)) return THOR_ERR_ARG;
+  if (!sse_fill_pair(pr, *orig, slot_planes(e, e->last_slot))) return THOR_ERR_ARG;
   EHIP(hipSetDevice(e->device));
   return ssim_enqueue(&pr, 1, e->W, e->H, (unsigned long long *)sums_dev, e->stream);
 }

@@ -1388,7 +1388,7 @@ TE_NOINL uint32_t te_motion_estimate(const TeFrame &F_, TeSB &sb_, int r, const 
   mv_opt.x = mv_opt.y = 0;
   mv_ref.y = (int16_t)((((int)mvc.y + 2) >> 2) << 2);
   mv_ref.x = (int16_t)((((int)mvc.x + 2) >> 2) << 2);
-#if !defined(TE_HOST) && !defined(TE_ME_SEQ)
+#if !defined(TE_HOST)
   TeMeBlk B;
   te_me_blk(B, org, os, width, height);
   auto mvcost = [&](TeMv c) -> uint32_t { return te_lambda_bits(lam, te_mv_bits(c.y - mvp.y, c.x - mvp.x)); };
@@ -1396,7 +1396,7 @@ TE_NOINL uint32_t te_motion_estimate(const TeFrame &F_, TeSB &sb_, int r, const 
 #endif
   if ((size == 16 && enable_bipred) || F.speed == 0) {  // telescope search
     int step = 32;
-#if !defined(TE_HOST) && !defined(TE_ME_SEQ)
+#if !defined(TE_HOST)
     // the 5 x 5 grid of a step, row-major, the centre skipped after the first step
     for (; step >= 4 && !(step == 32 && wide32); step >>= 1) {
       const TeMv ref0 = mv_ref;
@@ -1439,7 +1439,7 @@ TE_NOINL uint32_t te_motion_estimate(const TeFrame &F_, TeSB &sb_, int r, const 
       step >>= 1;
     }
   }
-#if !defined(TE_HOST) && !defined(TE_ME_SEQ)
+#if !defined(TE_HOST)
   if (size != 16) {  // candidate search (the size-16 candidates take widesad: one at a time below)
     const TeMv *cl = sb.mc.mv[r];
     auto cand = [&](int idx) -> TeMv {
@@ -1473,7 +1473,7 @@ TE_NOINL uint32_t te_motion_estimate(const TeFrame &F_, TeSB &sb_, int r, const 
   for (int step = 1; step < maxsteps; step++) {  // full-pel hexagon search
     const int8_t *diy = te_hex_dy, *dix = te_hex_dx;
     int dir = start - 1, best_dir = -1;
-#if !defined(TE_HOST) && !defined(TE_ME_SEQ)
+#if !defined(TE_HOST)
     {  // directions start .. end (cyclic), in order
       const int nd = (end - start + 6) % 6 + 1, st0 = start;
       const TeMv ref0 = mv_ref;
@@ -1515,7 +1515,7 @@ TE_NOINL uint32_t te_motion_estimate(const TeFrame &F_, TeSB &sb_, int r, const 
   uint32_t cmin = min_sad;
   if (F.speed == 0) {  // exact half- and quarter-pel search through the MC filters
     const int8_t *hm = te_hp_m, *hn = te_hp_n;
-#if !defined(TE_HOST) && !defined(TE_ME_SEQ)
+#if !defined(TE_HOST)
     {
       const TeMv ref0 = mv_ref;
       auto hcand = [&](int idx) -> TeMv {
@@ -1578,7 +1578,7 @@ TE_NOINL uint32_t te_motion_estimate(const TeFrame &F_, TeSB &sb_, int r, const 
         xdelta_qp = qn[i];
       }
     }
-#if !defined(TE_HOST) && !defined(TE_ME_SEQ)
+#if !defined(TE_HOST)
     }
 #endif
   } else {  // fast bilinear approximation

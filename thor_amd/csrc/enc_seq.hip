@@ -36,7 +36,12 @@
 // FIFO per priority class (stream s -> class s * 16 / n); a worker takes the
 // oldest ready task of the highest class, so the first streams run their whole
 // chains ahead and the last ones fill the idle capacity.
-// (unity build: follows enc.hip in libthor_amd.hip)
+// (unity build: follows enc.hip in libthor_amd.hip and continues it; the measuring
+// jobs' SSE is quality.hip's band sum)
+#include "frame_ops.h"  // SsePair
+
+__device__ __forceinline__ void sse_wave_band(const SsePair &P, int W, int H, int r0, int r1,
+                                              unsigned long long *sse);  // quality.hip
 
 #define TS_NCLS 16
 #define TS_MAX_JOBS 4096          // 12 bits of a queue item

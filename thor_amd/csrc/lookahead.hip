@@ -10,9 +10,7 @@
 //
 // Every value is an exact integer and the search winner is an unsigned minimum
 // of distinct keys, so neither depends on the order of reduction.
-// (unity build: follows ssim.hip in libthor_amd.hip; the global-address-space
-// pointer type and sse_ld4 are quality.hip's)
-#include "common.h"
+#include "frame_ops.h"
 
 #define LA_TBW 8    // blocks per tile row: 64 lowres pixels
 #define LA_TBH 4    // block rows per tile: 32 lowres pixels
@@ -33,10 +31,6 @@
 static_assert(LA_CUR_STRIDE % 4 == 0 && LA_REF_STRIDE % 4 == 0 && LA_CUR_BYTES % 4 == 0, "rows are whole dwords");
 static_assert(255 * 64 < (1 << 14) && 2 * LA_RANGE < (1 << 5) && LA_NCAND <= (1 << 9), "the key's three fields");
 
-struct LaPair {
-  const uint8_t *cur, *ref;  // luma interior (0, 0); ref nullptr: an intra-only pair
-  int cs, rs;                // strides
-};
 struct LaArgs {
   uint2 *blocks;             // [pairs * bw * bh] records, or nullptr
   unsigned long long *sums;  // [4 * pairs], zero before the launch
@@ -48,14 +42,14 @@ static_assert(sizeof(LaArgs) <= 1024, "the pairs travel in the kernarg segment")
 // Four lowres pixels (x .. x + 3, row y; both clamped to the plane) of the source plane p, packed in a dword.
 // A group inside the plane takes four dword loads (two source rows x 8 bytes, any alignment); a group across
 // the plane's edge goes pixel by pixel.  Nothing is read outside source rows [0, 2 lh) and columns [0, 2 lw).
-__device__ __forceinline__ uint32_t la_lowres4(sse_gptr p, int stride, int x, int y, int lw, int lh) {
+__device__ __forceinline__ uint32_t la_lowres4(gcptr p, int stride, int x, int y, int lw, int lh) {
   const int yc = min(max(y, 0), lh - 1);
-  const sse_gptr r0 = p + (long long)(2 * yc) * stride, r1 = r0 + stride;
+  const gcptr r0 = p + (long long)(2 * yc) * stride, r1 = r0 + stride;
   if (x >= 0 && x + 3 < lw) {
     uint32_t t[2];
 #pragma unroll
     for (int k = 0; k < 2; k++) {
-      const uint32_t a = sse_ld4(r0 + 2 * x + 4 * k), b = sse_ld4(r1 + 2 * x + 4 * k);
+      const uint32_t a = g_ld4(r0 + 2 * x + 4 * k), b = g_ld4(r1 + 2 * x + 4 * k);
       // two pixels at once in 16-bit fields: each sum <= 4 * 255 + 2
       const uint32_t s =
           (a & 0x00ff00ffu) + ((a >> 8) & 0x00ff00ffu) + (b & 0x00ff00ffu) + ((b >> 8) & 0x00ff00ffu) + 0x00020002u;
@@ -74,45 +68,12 @@ __device__ __forceinline__ uint32_t la_lowres4(sse_gptr p, int stride, int x, in
   return out;
 }
 
-// Wave minimum of a 32-bit value (all 64 lanes active, wave-uniform call site): sse_wave_sum's DPP steps.
-__device__ __forceinline__ uint32_t la_wave_min(uint32_t v) {
-  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
-  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
-  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x141, 0xF, 0xF, false));  // row_half_mirror
-  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x140, 0xF, 0xF, false));  // row_mirror
-  return min(min((uint32_t)__builtin_amdgcn_readlane((int)v, 0), (uint32_t)__builtin_amdgcn_readlane((int)v, 16)),
-             min((uint32_t)__builtin_amdgcn_readlane((int)v, 32), (uint32_t)__builtin_amdgcn_readlane((int)v, 48)));
-}
-
 typedef short la_s2 __attribute__((ext_vector_type(2)));
-
-// A DPP move inside the 16-lane rows (all lanes active: every lane has a source).
-template <int CTRL>
-__device__ __forceinline__ uint32_t la_dpp(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xF, 0xF, false);
-}
-// The value of lane ^ (1 << BIT) of the same row, BIT 0..3.  ^1 and ^2 are quad permutations, ^8 a rotation by
-// half a row; ^4 is row_half_mirror (^7) followed by a reversal of every quad (^3).
-template <int BIT>
-__device__ __forceinline__ uint32_t la_row_xor(uint32_t v) {
-  if (BIT == 0) return la_dpp<0xB1>(v);                // quad_perm [1,0,3,2]
-  if (BIT == 1) return la_dpp<0x4E>(v);                // quad_perm [2,3,0,1]
-  if (BIT == 2) return la_dpp<0x1B>(la_dpp<0x141>(v));  // quad_perm [3,2,1,0] of row_half_mirror
-  return la_dpp<0x128>(v);                             // row_ror:8
-}
-// Every lane: the sum of `v` over its 16-lane row.
-__device__ __forceinline__ uint32_t la_row_sum(uint32_t v) {
-  v += la_dpp<0xB1>(v);
-  v += la_dpp<0x4E>(v);
-  v += la_dpp<0x141>(v);  // row_half_mirror
-  v += la_dpp<0x140>(v);  // row_mirror
-  return v;
-}
 // One butterfly of two packed 16-bit values across lane bit BIT: the lane with the bit clear gets the sum, the
 // other the difference (sg: the lane's packed +1 or -1 for this bit).
 template <int BIT>
 __device__ __forceinline__ la_s2 la_butterfly(la_s2 v, la_s2 sg) {
-  const la_s2 p = __builtin_bit_cast(la_s2, la_row_xor<BIT>(__builtin_bit_cast(uint32_t, v)));
+  const la_s2 p = __builtin_bit_cast(la_s2, row_xor<BIT>(__builtin_bit_cast(uint32_t, v)));
   return p + v * sg;
 }
 
@@ -128,7 +89,7 @@ __global__ __launch_bounds__(256) void k_lookahead(const LaArgs A) {
   // (the inline pairs are read in place in the kernarg segment: a dynamic index into the by-value
   // argument would copy it to scratch)
   const LaPair *pp = ((const LaArgs *)__builtin_amdgcn_kernarg_segment_ptr())->inl + blockIdx.z;
-  const sse_gptr cur = (sse_gptr)pp->cur, ref = (sse_gptr)pp->ref;
+  const gcptr cur = (gcptr)pp->cur, ref = (gcptr)pp->ref;
   const int cs = pp->cs, rs = pp->rs;
   const bool inter_pair = pp->ref != nullptr;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -212,7 +173,7 @@ __global__ __launch_bounds__(256) void k_lookahead(const LaArgs A) {
         const uint32_t len = (uint32_t)(abs(dx - LA_RANGE) + abs(dy - LA_RANGE));
         best = min(best, (sad << 14) | (len << 9) | (uint32_t)(dy * LA_SIDE + dx));
       }
-      best = la_wave_min(best);
+      best = wave_reduce(best, OpMin());  // (all 64 lanes active: the branch is uniform)
     }
     const int wk = (int)(best & 511u), wdy = inter_pair ? wk / LA_SIDE : LA_RANGE;
     const int wdx = inter_pair ? wk - wdy * LA_SIDE : LA_RANGE;
@@ -221,7 +182,7 @@ __global__ __launch_bounds__(256) void k_lookahead(const LaArgs A) {
     const bool has_top = gby > 0, has_left = gbx > 0;  // (uniform)
     const int ea = lane < 8 ? cbase - LA_CUR_STRIDE + lane : cbase + ((lane - 8) & 7) * LA_CUR_STRIDE - 1;
     const uint32_t ev = (lane < 8 ? has_top : lane < 16 && has_left) ? (uint32_t)curb[ea] : 0u;
-    const uint32_t edge = (uint32_t)__builtin_amdgcn_readlane((int)la_row_sum(ev), 0);
+    const uint32_t edge = (uint32_t)__builtin_amdgcn_readlane((int)row_reduce(ev, OpSum()), 0);
     const uint32_t dc = has_top && has_left ? (edge + 8) >> 4 : has_top || has_left ? (edge + 4) >> 3 : 128u;
     // The four residuals, one per 16-lane row (rj: 0 the search winner, 1 DC, 2 V, 3 H); a lane takes four
     // pixels of a row of the block (row rr, columns 4 hf ..) and the same four of its row's predictor: two dwords
@@ -250,7 +211,7 @@ __global__ __launch_bounds__(256) void k_lookahead(const LaArgs A) {
     // (a lane's four magnitudes sum to at most 4 * 16 320, a row's to at most 130 560)
     const uint32_t mag =
         (uint32_t)abs((int)ta.x) + (uint32_t)abs((int)ta.y) + (uint32_t)abs((int)tb.x) + (uint32_t)abs((int)tb.y);
-    const uint32_t rowsum = la_row_sum(mag);
+    const uint32_t rowsum = row_reduce(mag, OpSum());
     const uint32_t s_dc = ((uint32_t)__builtin_amdgcn_readlane((int)rowsum, 16) + 2) >> 2;
     const uint32_t s_v = has_top ? ((uint32_t)__builtin_amdgcn_readlane((int)rowsum, 32) + 2) >> 2 : 0xffffffffu;
     const uint32_t s_h = has_left ? ((uint32_t)__builtin_amdgcn_readlane((int)rowsum, 48) + 2) >> 2 : 0xffffffffu;
@@ -277,31 +238,20 @@ __global__ __launch_bounds__(256) void k_lookahead(const LaArgs A) {
   if (tid < 4 && wsum[tid]) atomicAdd(A.sums + 4 * (size_t)blockIdx.z + tid, (unsigned long long)wsum[tid]);
 }
 
-static inline void la_dims(int W, int H, int &lw, int &lh, int &bw, int &bh) {
-  lw = W >> 1, lh = H >> 1;
-  bw = lw >> 3, bh = lh >> 3;
-}
-
 // Zero the sums and launch k_lookahead for n pairs on `st`, LA_INL per launch through the kernel arguments.
 static int la_enqueue(const LaPair *host, int n, int W, int H, thor_la_block_t *blocks, unsigned long long *sums,
                       hipStream_t st) {
-  if (hipMemsetAsync(sums, 0, (size_t)n * 4 * sizeof(unsigned long long), st) != hipSuccess) {
-    (void)hipGetLastError();
-    return THOR_ERR_HIP;
-  }
+  if (zero_sums(sums, (size_t)n * 4, st) != THOR_OK) return THOR_ERR_HIP;
   LaArgs A;
   memset(&A, 0, sizeof(A));
   la_dims(W, H, A.lw, A.lh, A.bw, A.bh);
   const dim3 grid((unsigned)((A.bw + LA_TBW - 1) / LA_TBW), (unsigned)((A.bh + LA_TBH - 1) / LA_TBH), 1);
-  for (int i0 = 0; i0 < n; i0 += LA_INL) {
-    const int m = n - i0 < LA_INL ? n - i0 : LA_INL;
+  return launch_batches(n, LA_INL, [&](int i0, int m) {
     memcpy(A.inl, host + i0, (size_t)m * sizeof(LaPair));
     A.sums = sums + 4 * (size_t)i0;
     A.blocks = blocks ? (uint2 *)blocks + (size_t)i0 * A.bw * A.bh : nullptr;
     k_lookahead<<<dim3(grid.x, grid.y, (unsigned)m), 256, 0, st>>>(A);
-  }
-  if (hipGetLastError() != hipSuccess) return THOR_ERR_HIP;
-  return THOR_OK;
+  });
 }
 
 extern "C" {
@@ -322,13 +272,9 @@ int thor_lookahead_i420(const thor_yuv_planes_t *cur, const thor_yuv_planes_t *r
   if (((uintptr_t)blocks_dev | (uintptr_t)sums_dev) & 7) return THOR_ERR_ARG;  // (a record leaves as one 8-byte store)
   std::vector<LaPair> pairs((size_t)n);
   for (int i = 0; i < n; i++) {
-    if (!cur[i].y || cur[i].stride_y < width) return THOR_ERR_ARG;
-    pairs[i].cur = cur[i].y, pairs[i].cs = cur[i].stride_y;
-    pairs[i].ref = nullptr, pairs[i].rs = 0;
-    if (ref && ref[i].y) {
-      if (ref[i].stride_y < width) return THOR_ERR_ARG;
-      pairs[i].ref = ref[i].y, pairs[i].rs = ref[i].stride_y;
-    }
+    if (!cur[i].y || cur[i].stride_y < width) return THOR_ERR_ARG;  // (luma only: the chroma planes are not read)
+    la_fill_pair(pairs[i], cur[i], ref ? ref + i : nullptr);
+    if (pairs[i].ref && pairs[i].rs < width) return THOR_ERR_ARG;
   }
   return la_enqueue(pairs.data(), n, width, height, blocks_dev, (unsigned long long *)sums_dev, (hipStream_t)stream);
 }

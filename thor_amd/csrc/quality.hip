@@ -8,10 +8,10 @@
 // The sums are exact integers, so the order of summation does not matter:
 // every wave adds its band's sum to the pair's 64-bit totals with one integer
 // atomic per plane.
-// (unity build: follows capi.hip in libthor_amd.hip)
+// The decoder context, find_slot_host and HIPCHK are capi.hip's.
 #include <math.h>
 
-#include "common.h"
+#include "frame_ops.h"
 
 #define SSE_BAND 8  // luma rows (and the 4 chroma rows under them) per wave
 #define SSE_INL 8   // frame pairs that travel in the kernel arguments (64 bytes each)
@@ -21,10 +21,6 @@
 #define SSE_SPILL 64
 static_assert(64LL * SSE_SPILL * 16 * 255 * 255 < (1LL << 32), "a wave's 32-bit partial must hold its pixels");
 
-struct SsePair {
-  const uint8_t *a[3], *b[3];  // Y, U, V interior (0, 0)
-  int as[2], bs[2];            // luma / chroma stride
-};
 struct SseArgs {
   const SsePair *dev;  // the pairs in device memory, or nullptr: inl[]
   unsigned long long *sse;  // [3 * pairs], zero before the launch
@@ -33,22 +29,11 @@ struct SseArgs {
 };
 static_assert(sizeof(SseArgs) <= 1024, "the pairs travel in the kernarg segment");
 
-// The planes are in global memory: loads through pointers of that address space are global_load_*
-// (the generic pointers of a plane set would make them flat_load_*, which wait on both memory counters
-// and cannot take the unaligned dword form).
-typedef const __attribute__((address_space(1))) uint8_t *sse_gptr;
-typedef uint32_t sse_v4 __attribute__((ext_vector_type(4)));  // (a native vector: loads through an address-space pointer)
-typedef const __attribute__((address_space(1))) sse_v4 *sse_gptr16;
-typedef uint32_t __attribute__((aligned(1))) sse_u32u;
-__device__ __forceinline__ uint32_t sse_ld4(sse_gptr p) { return *(const __attribute__((address_space(1))) sse_u32u *)p; }
-
-// Wave sum of a 32-bit value (all 64 lanes active, wave-uniform call site): DPP
-// inside each 16-lane row, the four rows through readlane (enc_core.h's te_sum).
+// Wave sum of a 32-bit value (all 64 lanes active, wave-uniform call site).  frame_ops.h's wave_reduce but for
+// its last step: that one folds the four rows pairwise, and the compiler schedules the pairwise sum differently
+// from the chain this kernel has always had, so the chain stays.
 __device__ __forceinline__ uint32_t sse_wave_sum(uint32_t v) {
-  v += (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
-  v += (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
-  v += (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x141, 0xF, 0xF, false);  // row_half_mirror
-  v += (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x140, 0xF, 0xF, false);  // row_mirror
+  v = row_reduce(v, OpSum());
   return (uint32_t)__builtin_amdgcn_readlane((int)v, 0) + (uint32_t)__builtin_amdgcn_readlane((int)v, 16) +
          (uint32_t)__builtin_amdgcn_readlane((int)v, 32) + (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
 }
@@ -66,7 +51,7 @@ __device__ __forceinline__ uint32_t sse_wave_sum(uint32_t v) {
 // SSE_SPILL passes per lane (65 536 pixels per wave, the limit is 66 051).
 __device__ __forceinline__ unsigned long long sse_wave_rows(const uint8_t *a_, int as, const uint8_t *b_, int bs, int w,
                                                             int r0, int r1) {
-  const sse_gptr a = (sse_gptr)a_, b = (sse_gptr)b_;
+  const gcptr a = (gcptr)a_, b = (gcptr)b_;
   const int lane = threadIdx.x & 63;
   const int nc = (w + 15) >> 4, total = (r1 - r0) * nc;
   if (total <= 0) return 0;
@@ -79,15 +64,15 @@ __device__ __forceinline__ unsigned long long sse_wave_rows(const uint8_t *a_, i
   for (int g0 = 0; g0 < total; g0 += 64) {
     if (g0 + lane < total) {
       const int x = c << 4, n = min(16, w - x);
-      const sse_gptr pa = a + (long long)(r0 + row) * as + x, pb = b + (long long)(r0 + row) * bs + x;
+      const gcptr pa = a + (long long)(r0 + row) * as + x, pb = b + (long long)(r0 + row) * bs + x;
       if (n == 16) {
-        sse_v4 u, v;
+        u32x4 u, v;
         if (wide) {
-          u = *(sse_gptr16)pa;
-          v = *(sse_gptr16)pb;
+          u = *(gcptr16)pa;
+          v = *(gcptr16)pb;
         } else {
-          u = sse_v4{sse_ld4(pa), sse_ld4(pa + 4), sse_ld4(pa + 8), sse_ld4(pa + 12)};
-          v = sse_v4{sse_ld4(pb), sse_ld4(pb + 4), sse_ld4(pb + 8), sse_ld4(pb + 12)};
+          u = g_ld4x4(pa);
+          v = g_ld4x4(pb);
         }
         s = __builtin_amdgcn_udot4(u.x, u.x, s, false);
         s = __builtin_amdgcn_udot4(v.x, v.x, s, false);
@@ -104,7 +89,7 @@ __device__ __forceinline__ unsigned long long sse_wave_rows(const uint8_t *a_, i
       } else {
         int j = 0;
         for (; j + 4 <= n; j += 4) {
-          const uint32_t u = sse_ld4(pa + j), v = sse_ld4(pb + j);
+          const uint32_t u = g_ld4(pa + j), v = g_ld4(pb + j);
           s = __builtin_amdgcn_udot4(u, u, s, false);
           s = __builtin_amdgcn_udot4(v, v, s, false);
           ab = __builtin_amdgcn_udot4(u, v, ab, false);
@@ -156,42 +141,22 @@ __global__ __launch_bounds__(256) void k_sse_i420(const SseArgs A) {
   sse_wave_band(P, A.W, A.H, r0, min(r0 + SSE_BAND, A.H), A.sse + 3 * (size_t)i);
 }
 
-static inline bool sse_fill_pair(SsePair &P, const thor_yuv_planes_t &a, const thor_yuv_planes_t &b) {
-  if (!a.y || !a.u || !a.v || !b.y || !b.u || !b.v) return false;
-  P.a[0] = a.y, P.a[1] = a.u, P.a[2] = a.v;
-  P.b[0] = b.y, P.b[1] = b.u, P.b[2] = b.v;
-  P.as[0] = a.stride_y, P.as[1] = a.stride_c;
-  P.bs[0] = b.stride_y, P.bs[1] = b.stride_c;
-  return true;
-}
-
 // Zero the sums and launch k_sse_i420 for n pairs on `st`: the pairs in device memory (`dev`, one
 // launch) or on the host (`host`, SSE_INL per launch through the kernel arguments).
 static int sse_enqueue(const SsePair *dev, const SsePair *host, int n, int W, int H, unsigned long long *sse,
                        hipStream_t st) {
-  if (hipMemsetAsync(sse, 0, (size_t)n * 3 * sizeof(unsigned long long), st) != hipSuccess) {
-    (void)hipGetLastError();
-    return THOR_ERR_HIP;
-  }
+  if (zero_sums(sse, (size_t)n * 3, st) != THOR_OK) return THOR_ERR_HIP;
   const unsigned gx = (unsigned)((H + 4 * SSE_BAND - 1) / (4 * SSE_BAND));
   SseArgs A;
   memset(&A, 0, sizeof(A));
   A.W = W;
   A.H = H;
-  if (dev) {
-    A.dev = dev;
-    A.sse = sse;
-    k_sse_i420<<<dim3(gx, (unsigned)n), 256, 0, st>>>(A);
-  } else {
-    for (int i0 = 0; i0 < n; i0 += SSE_INL) {
-      const int m = n - i0 < SSE_INL ? n - i0 : SSE_INL;
-      memcpy(A.inl, host + i0, (size_t)m * sizeof(SsePair));
-      A.sse = sse + 3 * (size_t)i0;
-      k_sse_i420<<<dim3(gx, (unsigned)m), 256, 0, st>>>(A);
-    }
-  }
-  if (hipGetLastError() != hipSuccess) return THOR_ERR_HIP;
-  return THOR_OK;
+  A.dev = dev;
+  return launch_batches(n, dev ? n : SSE_INL, [&](int i0, int m) {
+    if (!dev) memcpy(A.inl, host + i0, (size_t)m * sizeof(SsePair));
+    A.sse = sse + 3 * (size_t)i0;
+    k_sse_i420<<<dim3(gx, (unsigned)m), 256, 0, st>>>(A);
+  });
 }
 
 extern "C" {
@@ -216,10 +181,8 @@ int thor_dec_frame_sse(thor_dec_t *d, int frame_num, const thor_yuv_planes_t *or
   if (!d || !orig || !sse_dev) return THOR_ERR_ARG;
   const int s = find_slot_host(d, frame_num);
   if (s < 0) return THOR_ERR_REF;
-  uint8_t *base = d->slots + (long long)s * d->slot_bytes;
-  const thor_yuv_planes_t rec = {base + d->offy, base + d->offu, base + d->offv, d->sy, d->sc};
   SsePair P;
-  if (!sse_fill_pair(P, *orig, rec)) return THOR_ERR_ARG;
+  if (!sse_fill_pair(P, *orig, slot_planes(d, s))) return THOR_ERR_ARG;
   HIPCHK(hipSetDevice(d->device));
   return sse_enqueue(nullptr, &P, 1, d->seq.width, d->seq.height, (unsigned long long *)sse_dev, d->stream);
 }

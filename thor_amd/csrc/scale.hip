@@ -10,8 +10,9 @@
 // once), filters each chunk horizontally into an LDS intermediate (int16, 6
 // fractional bits, two rows per word), then runs the vertical pass from there;
 // both passes are v_dot2_i32_i16 on pairs of taps.
-// (unity build: follows color.hip in libthor_amd.hip)
-#include "common.h"
+// The decoder context and HIPCHK are capi.hip's; thor_dec_frame_scaled takes the slot from color.hip's
+// thor_dec_frame_planes.
+#include "frame_ops.h"
 #include "scale_host.h"
 
 #define SCALE_INL THOR_SCALE_LAUNCH_IMAGES  // images that travel in the kernel arguments (64 bytes each)
@@ -52,9 +53,6 @@ struct thor_scaler {
   size_t lds;
 };
 
-typedef __attribute__((address_space(1))) uint8_t *scl_gp;
-typedef const __attribute__((address_space(1))) uint8_t *scl_cgp;
-typedef uint32_t __attribute__((aligned(1))) scl_u32u;
 typedef short scl_s2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ int scl_dot2(uint32_t a, uint32_t b, int c) {
@@ -70,7 +68,7 @@ __device__ __forceinline__ uint32_t scl_byte(int acc) {
   return (uint32_t)v;
 }
 
-__device__ __forceinline__ int scl_mis(scl_cgp p) { return (int)((unsigned long long)p & 3u); }
+__device__ __forceinline__ int scl_mis(gcptr p) { return (int)((unsigned long long)p & 3u); }
 
 // What a lane holds of the next chunk while the current one is filtered: its dwords of the source window,
 // and with a tile's first chunk its words of the tile's horizontal table.
@@ -82,14 +80,14 @@ struct ScalePre {
 };
 
 // Issue the loads of chunk c (rows [c cr, c cr + rows)) of tile column t; nothing waits here.
-__device__ __forceinline__ void scl_fetch(const ScalePlane &P, scl_cgp plane, int sstride, int y0, int nrows, int t, int c,
+__device__ __forceinline__ void scl_fetch(const ScalePlane &P, gcptr plane, int sstride, int y0, int nrows, int t, int c,
                                           int tid, ScalePre &R) {
   // the tile's source span [xs0, xs0 + span) lies inside the row (start[] is clamped on the host), span + 3 <= 4 ndw
   R.xs0 = P.hstart[t * 64];
   R.span = P.hstart[t * 64 + 63] + P.ntH - R.xs0;  // (uniform)
   R.myoff = P.hstart[t * 64 + (tid & 63)] - R.xs0;
   const int ndw = P.ndw, rows = min(P.cr, nrows - c * P.cr), total = rows * ndw;
-  const scl_cgp win = plane + (long long)(y0 + c * P.cr) * sstride + R.xs0;
+  const gcptr win = plane + (long long)(y0 + c * P.cr) * sstride + R.xs0;
   // Aligned dwords only: a row is fetched from its span's address rounded down to 4 (scl_mis bytes earlier),
   // so the up to 3 bytes read before and after the span share a dword with a sample of the span.
 #pragma unroll
@@ -97,7 +95,7 @@ __device__ __forceinline__ void scl_fetch(const ScalePlane &P, scl_cgp plane, in
     if (256 * k >= total) break;  // (uniform)
     const int idx = 256 * k + tid;
     const int rr = recon_div((unsigned)idx, P.mndw), b = 4 * (idx - rr * ndw);
-    const scl_cgp p = win + (long long)rr * sstride;
+    const gcptr p = win + (long long)rr * sstride;
     const int mis = scl_mis(p);
     uint32_t v = 0;
     if (idx < total && b < R.span + mis) v = *(const __attribute__((address_space(1))) uint32_t *)(p - mis + b);
@@ -140,7 +138,7 @@ __global__ __launch_bounds__(256) void k_scale_i420(const ScaleArgs A) {
 
   const int y0 = P.vy0[2 * by], nrows = P.vy0[2 * by + 1];
   const int nch = (nrows + P.cr - 1) / P.cr, nwork = min(SCALE_TPB, P.tx - t0) * nch;
-  const scl_cgp plane = (scl_cgp)I.s[pc];
+  const gcptr plane = (gcptr)I.s[pc];
   ScalePre R;
   scl_fetch(P, plane, sstride, y0, nrows, t0, 0, tid, R);
   // the tile row's vertical table (made visible by the loop's first barrier)
@@ -196,9 +194,9 @@ __global__ __launch_bounds__(256) void k_scale_i420(const ScaleArgs A) {
       a3 = scl_dot2(v.w, cf, a3);
     }
     const uint32_t b0 = scl_byte(a0), b1 = scl_byte(a1), b2 = scl_byte(a2), b3 = scl_byte(a3);
-    const scl_gp out = (scl_gp)I.d[pc] + (long long)e * dstride + (unsigned)d0;
+    const gptr out = (gptr)I.d[pc] + (long long)e * dstride + (unsigned)d0;
     if (d0 + 3 < P.dw) {
-      *(__attribute__((address_space(1))) scl_u32u *)out = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+      g_st4(out, b0 | (b1 << 8) | (b2 << 16) | (b3 << 24));
     } else {  // the row's ragged end: sample by sample, nothing past dw
       out[0] = (uint8_t)b0;
       if (d0 + 1 < P.dw) out[1] = (uint8_t)b1;
@@ -210,11 +208,8 @@ __global__ __launch_bounds__(256) void k_scale_i420(const ScaleArgs A) {
 // Everything that can be refused without a device: THOR_OK or THOR_ERR_ARG.
 static int scale_check_images(const thor_scaler *s, const thor_yuv_planes_t *src, const thor_yuv_planes_t *dst, int n) {
   if (!s || !src || !dst || n <= 0 || n > 65535) return THOR_ERR_ARG;
-  for (int i = 0; i < n; i++) {
-    if (!src[i].y || !src[i].u || !src[i].v || !dst[i].y || !dst[i].u || !dst[i].v) return THOR_ERR_ARG;
-    if (src[i].stride_y < s->sw || src[i].stride_c < (s->sw >> 1)) return THOR_ERR_ARG;
-    if (dst[i].stride_y < s->dw || dst[i].stride_c < (s->dw >> 1)) return THOR_ERR_ARG;
-  }
+  for (int i = 0; i < n; i++)
+    if (!planes_ok(src[i], s->sw) || !planes_ok(dst[i], s->dw)) return THOR_ERR_ARG;
   return THOR_OK;
 }
 
@@ -225,16 +220,13 @@ static int scale_enqueue(const thor_scaler *s, const thor_yuv_planes_t *src, con
   memset(&A, 0, sizeof(A));
   A.pl[0] = s->pl[0];
   A.pl[1] = s->pl[1];
-  for (int i0 = 0; i0 < n; i0 += SCALE_INL) {
-    const int m = n - i0 < SCALE_INL ? n - i0 : SCALE_INL;
+  return launch_batches(n, SCALE_INL, [&](int i0, int m) {
     for (int i = 0; i < m; i++) {
       const thor_yuv_planes_t &a = src[i0 + i], &b = dst[i0 + i];
       A.img[i] = ScaleImg{{a.y, a.u, a.v}, {b.y, b.u, b.v}, a.stride_y, a.stride_c, b.stride_y, b.stride_c};
     }
     k_scale_i420<<<dim3((unsigned)((s->pl[0].tx + SCALE_TPB - 1) / SCALE_TPB), (unsigned)s->pl[0].ty, (unsigned)(3 * m)), 256, s->lds, st>>>(A);
-  }
-  if (hipGetLastError() != hipSuccess) return THOR_ERR_HIP;
-  return THOR_OK;
+  });
 }
 
 extern "C" {

@@ -9,11 +9,10 @@
 // The sums are exact integers, so the order of summation does not matter:
 // every wave adds its windows' sum to the pair's 64-bit plane total with one
 // integer atomic (two's complement: q is negative where the covariance is).
-// (unity build: follows scale.hip in libthor_amd.hip; the plane pairs, the
-// global-address-space pointer types and sse_ld4 are quality.hip's)
+// The decoder context, find_slot_host and HIPCHK are capi.hip's.
 #include <math.h>
 
-#include "common.h"
+#include "frame_ops.h"
 
 #define SSIM_BAND 16   // window rows per wave: SSIM_BAND + 1 block rows are read
 #define SSIM_LANES 63  // lanes of a wave that own windows: four each; lane 63 only lends lane 62 its first block
@@ -38,27 +37,27 @@ static __host__ __device__ inline int ssim_bands(int bh) { return (bh - 1 + SSIM
 // pa / pb: the lane's first pixel of the block row; nb: how many of its four blocks lie inside the plane
 // (FULL: four in every lane; wide: 16-byte loads).  Nothing is read outside those nb blocks.
 template <bool FULL>
-__device__ __forceinline__ void ssim_block_row(sse_gptr pa, int as, sse_gptr pb, int bs, int nb, bool wide, uint32_t p[4],
+__device__ __forceinline__ void ssim_block_row(gcptr pa, int as, gcptr pb, int bs, int nb, bool wide, uint32_t p[4],
                                                uint32_t ss[4], uint32_t s12[4]) {
   uint32_t s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
 #pragma unroll
   for (int k = 0; k < 4; k++) ss[k] = s12[k] = 0;
 #pragma unroll
   for (int y = 0; y < 4; y++) {
-    const sse_gptr ra = pa + (long long)y * as, rb = pb + (long long)y * bs;
-    sse_v4 u = {0, 0, 0, 0}, v = {0, 0, 0, 0};
+    const gcptr ra = pa + (long long)y * as, rb = pb + (long long)y * bs;
+    u32x4 u = {0, 0, 0, 0}, v = {0, 0, 0, 0};
     if (FULL || nb == 4) {
       if (wide) {
-        u = *(sse_gptr16)ra;
-        v = *(sse_gptr16)rb;
+        u = *(gcptr16)ra;
+        v = *(gcptr16)rb;
       } else {
-        u = sse_v4{sse_ld4(ra), sse_ld4(ra + 4), sse_ld4(ra + 8), sse_ld4(ra + 12)};
-        v = sse_v4{sse_ld4(rb), sse_ld4(rb + 4), sse_ld4(rb + 8), sse_ld4(rb + 12)};
+        u = g_ld4x4(ra);
+        v = g_ld4x4(rb);
       }
     } else {
-      if (nb > 0) u.x = sse_ld4(ra), v.x = sse_ld4(rb);
-      if (nb > 1) u.y = sse_ld4(ra + 4), v.y = sse_ld4(rb + 4);
-      if (nb > 2) u.z = sse_ld4(ra + 8), v.z = sse_ld4(rb + 8);
+      if (nb > 0) u.x = g_ld4(ra), v.x = g_ld4(rb);
+      if (nb > 1) u.y = g_ld4(ra + 4), v.y = g_ld4(rb + 4);
+      if (nb > 2) u.z = g_ld4(ra + 8), v.z = g_ld4(rb + 8);
     }
 #pragma unroll
     for (int k = 0; k < 4; k++) {
@@ -90,7 +89,7 @@ __device__ __forceinline__ int ssim_q(uint32_t s1, uint32_t s2, uint32_t ss, uin
 // The wave marches down the block rows keeping the previous row's sums in registers; a window is
 // two block rows x two blocks, the fifth block of a lane's four windows is its neighbour's first.
 template <bool FULL>
-__device__ __forceinline__ long long ssim_wave_tile(sse_gptr pa, int as, sse_gptr pb, int bs, int nb, int nwin, bool wide,
+__device__ __forceinline__ long long ssim_wave_tile(gcptr pa, int as, gcptr pb, int bs, int nb, int nwin, bool wide,
                                                     int nrows) {
   const int next = (((int)(threadIdx.x & 63) + 1) & 63) << 2;  // ds_bpermute address of the lane to the right
   uint32_t pp[4], pss[4], ps12[4];
@@ -119,13 +118,6 @@ __device__ __forceinline__ long long ssim_wave_tile(sse_gptr pa, int as, sse_gpt
     }
   }
   return tot;
-}
-
-// Wave sum of a 64-bit value (all 64 lanes active, wave-uniform call site).
-__device__ __forceinline__ long long ssim_wave_sum(long long v) {
-#pragma unroll
-  for (int m = 32; m; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
 }
 
 // grid (ceil(units / 4), pairs), 256 threads: a wave takes one unit of pair blockIdx.y.  The units of a
@@ -157,35 +149,29 @@ __global__ __launch_bounds__(256) void k_ssim_i420(const SsimArgs A) {
   const int bx0 = tile * SSIM_TILE + 4 * lane;                                // the lane's first block
   const int nb = min(max(bw - bx0, 0), 4);                                    // its blocks inside the plane
   const int nwin = lane < SSIM_LANES ? min(max(bw - 1 - bx0, 0), 4) : 0;      // the windows it owns
-  const sse_gptr pa = (sse_gptr)a_ + 4LL * r0 * as + 4 * bx0, pb = (sse_gptr)b_ + 4LL * r0 * bs + 4 * bx0;
+  const gcptr pa = (gcptr)a_ + 4LL * r0 * as + 4 * bx0, pb = (gcptr)b_ + 4LL * r0 * bs + 4 * bx0;
   long long tot;
   if (tile * SSIM_TILE + 256 <= bw)  // (uniform) every lane's four blocks are inside the plane
     tot = ssim_wave_tile<true>(pa, as, pb, bs, 4, nwin, wide, nrows);
   else
     tot = ssim_wave_tile<false>(pa, as, pb, bs, nb, nwin, wide, nrows);
-  tot = ssim_wave_sum(tot);
+  tot = wave_sum64(tot);  // (all 64 lanes active: the tile's partial loads have reconverged)
   if (lane == 0 && tot) atomicAdd(A.sums + 3 * (size_t)blockIdx.y + pl, (unsigned long long)tot);
 }
 
 // Zero the sums and launch k_ssim_i420 for n pairs on `st`, SSIM_INL per launch through the kernel arguments.
 static int ssim_enqueue(const SsePair *host, int n, int W, int H, unsigned long long *sums, hipStream_t st) {
-  if (hipMemsetAsync(sums, 0, (size_t)n * 3 * sizeof(unsigned long long), st) != hipSuccess) {
-    (void)hipGetLastError();
-    return THOR_ERR_HIP;
-  }
+  if (zero_sums(sums, (size_t)n * 3, st) != THOR_OK) return THOR_ERR_HIP;
   const int units = ssim_tiles(W >> 2) * ssim_bands(H >> 2) + 2 * ssim_tiles(W >> 3) * ssim_bands(H >> 3);
   SsimArgs A;
   memset(&A, 0, sizeof(A));
   A.W = W;
   A.H = H;
-  for (int i0 = 0; i0 < n; i0 += SSIM_INL) {
-    const int m = n - i0 < SSIM_INL ? n - i0 : SSIM_INL;
+  return launch_batches(n, SSIM_INL, [&](int i0, int m) {
     memcpy(A.inl, host + i0, (size_t)m * sizeof(SsePair));
     A.sums = sums + 3 * (size_t)i0;
     k_ssim_i420<<<dim3((unsigned)((units + 3) / 4), (unsigned)m), 256, 0, st>>>(A);
-  }
-  if (hipGetLastError() != hipSuccess) return THOR_ERR_HIP;
-  return THOR_OK;
+  });
 }
 
 extern "C" {
@@ -215,10 +201,8 @@ int thor_dec_frame_ssim(thor_dec_t *d, int frame_num, const thor_yuv_planes_t *o
   if (!d || !orig || !sums_dev || d->seq.width < 16 || d->seq.height < 16) return THOR_ERR_ARG;
   const int s = find_slot_host(d, frame_num);
   if (s < 0) return THOR_ERR_REF;
-  uint8_t *base = d->slots + (long long)s * d->slot_bytes;
-  const thor_yuv_planes_t rec = {base + d->offy, base + d->offu, base + d->offv, d->sy, d->sc};
   SsePair P;
-  if (!sse_fill_pair(P, *orig, rec)) return THOR_ERR_ARG;
+  if (!sse_fill_pair(P, *orig, slot_planes(d, s))) return THOR_ERR_ARG;
   HIPCHK(hipSetDevice(d->device));
   return ssim_enqueue(&P, 1, d->seq.width, d->seq.height, (unsigned long long *)sums_dev, d->stream);
 }

@@ -11,9 +11,11 @@
 // Every value is an exact integer and the search winners are unsigned minima of
 // distinct keys, so nothing depends on the order of reduction.  The per-pixel
 // division is the plain integer `/`.
-// (unity build: follows lookahead.hip in libthor_amd.hip; sse_gptr and sse_ld4 are
-// quality.hip's, LaPair, la_enqueue, la_dims, la_dpp and la_row_sum lookahead.hip's)
-#include "common.h"
+// The coarse stage is the lookahead's: la_enqueue (lookahead.hip) runs before the two kernels here.
+#include "frame_ops.h"
+
+static int la_enqueue(const LaPair *host, int n, int W, int H, thor_la_block_t *blocks, unsigned long long *sums,
+                      hipStream_t st);  // lookahead.hip
 
 #define TF_BLK 16    // a wave's luma block: four 8x8 sub-blocks that share the lookahead's start vector
 #define TF_WAVES 4   // waves of a workgroup, side by side: a tile of 64 x 16 luma pixels
@@ -58,15 +60,6 @@ struct TfArgs {
 };
 static_assert(sizeof(TfTarget) == 192 && sizeof(TfArgs) <= 1024, "the targets travel in the kernarg segment");
 
-// Every lane: the least `v` of its 16-lane row (all lanes active).
-__device__ __forceinline__ uint32_t tf_row_min(uint32_t v) {
-  v = min(v, la_dpp<0xB1>(v));
-  v = min(v, la_dpp<0x4E>(v));
-  v = min(v, la_dpp<0x141>(v));  // row_half_mirror
-  v = min(v, la_dpp<0x140>(v));  // row_mirror
-  return v;
-}
-
 // (a + b + c + d + 2) >> 2 of four packed bytes.  With b = a, c = a, d = a it is a; with c = a, d = b it is
 // (a + b + 1) >> 1: the contract's four prediction cases are this one form with the taps chosen by the fractions.
 __device__ __forceinline__ uint32_t tf_avg4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
@@ -94,16 +87,6 @@ __device__ __forceinline__ void tf_row5(const uint32_t *win, int row, int col, u
   const uint32_t w0 = p[0], w1 = p[1];
   lo = __builtin_amdgcn_alignbyte(w1, w0, sh);
   ex = w1 >> (8 * sh);
-}
-
-// Four pixels (x .. x + 3, row y; both clamped to the plane) of plane p, packed in a dword.
-__device__ __forceinline__ uint32_t tf_load4(sse_gptr p, int stride, int x, int y, int w, int h) {
-  const sse_gptr r = p + (long long)min(max(y, 0), h - 1) * stride;
-  if (x >= 0 && x + 3 < w) return sse_ld4(r + x);
-  uint32_t out = 0;
-#pragma unroll
-  for (int k = 0; k < 4; k++) out |= (uint32_t)r[min(max(x + k, 0), w - 1)] << (8 * k);
-  return out;
 }
 
 // Four output bytes at p: one dword where it is aligned, bytes elsewhere.
@@ -146,7 +129,7 @@ __global__ __launch_bounds__(256) void k_tf_luma(const TfArgs A) {
   if (tid < TF_LUT_WORDS) lut[tid] = tf_lut_dev[tid];
   if (live) {
     const int px = x0 + 4 * (lane & 3), py = y0 + (lane >> 2);
-    curw[lane] = px < A.w && py < A.h ? sse_ld4((sse_gptr)tg->cur[0] + (long long)py * cs + px) : 0u;
+    curw[lane] = px < A.w && py < A.h ? g_ld4((gcptr)tg->cur[0] + (long long)py * cs + px) : 0u;
   }
   __syncthreads();
   uint32_t c0[8], c1[8];
@@ -162,7 +145,7 @@ __global__ __launch_bounds__(256) void k_tf_luma(const TfArgs A) {
 
   const size_t rec_target = (size_t)blockIdx.z * A.nrefs;
   for (int r = 0; r < A.nrefs; r++) {
-    const sse_gptr ref = (sse_gptr)tg->ref[r][0];
+    const gcptr ref = (gcptr)tg->ref[r][0];
     const int rs = tg->rs[r][0];
     uint32_t *const rec = A.recs + ((rec_target + r) * A.bh8 + (2 * Y + sby)) * A.bw8 + 2 * X + sbx;
     if (!ref) {  // (uniform in the workgroup) an absent reference: zero records, no weight
@@ -178,7 +161,7 @@ __global__ __launch_bounds__(256) void k_tf_luma(const TfArgs A) {
     if (live)
       for (int g = lane; g < TF_WIN_WORDS; g += 64) {
         const int ry = g / (TF_WIN_STRIDE / 4), gx = g - ry * (TF_WIN_STRIDE / 4);
-        win[g] = tf_load4(ref, rs, x0 + sx - TF_MARGIN + 4 * gx, y0 + sy - TF_MARGIN + ry, A.w, A.h);
+        win[g] = ld4_clamped(ref, rs, x0 + sx - TF_MARGIN + 4 * gx, y0 + sy - TF_MARGIN + ry, A.w, A.h);
       }
     __syncthreads();
     if (!live) continue;  // (uniform in the wave; nothing below has a barrier)
@@ -201,7 +184,7 @@ __global__ __launch_bounds__(256) void k_tf_luma(const TfArgs A) {
       }
       best = min(best, (sad << 10) | ((uint32_t)(abs(dx) + abs(dy)) << 5) | (uint32_t)k);
     }
-    best = tf_row_min(best);
+    best = row_reduce(best, OpMin());  // (all 64 lanes active here and below: `live` is uniform in the wave)
     const int wk = (int)(best & 31u), oy = wk / (2 * TF_IR + 1) - TF_IR, ox = wk - (oy + TF_IR) * (2 * TF_IR + 1) - TF_IR;
 
     // half-pel refinement: candidate k = (hy + 1) * 3 + hx + 1 (the lanes past 8 repeat 8).  The half-pel vector
@@ -226,7 +209,7 @@ __global__ __launch_bounds__(256) void k_tf_luma(const TfArgs A) {
         sad = __builtin_amdgcn_sad_u8(tf_avg4(ahi, bhi, chi, dhi), c1[j], sad);
         alo = nlo, ahi = nhi, aex = nex;
       }
-      best = tf_row_min((sad << 6) | ((uint32_t)(abs(hx) + abs(hy)) << 4) | (uint32_t)k);
+      best = row_reduce((sad << 6) | ((uint32_t)(abs(hx) + abs(hy)) << 4) | (uint32_t)k, OpMin());
     }
     const int hk = (int)(best & 15u), hy = hk / 3 - 1, hx = hk - (hy + 1) * 3 - 1;
     const int mvx = 2 * (sx + ox) + hx, mvy = 2 * (sy + oy) + hy;
@@ -248,7 +231,7 @@ __global__ __launch_bounds__(256) void k_tf_luma(const TfArgs A) {
       df[k] = (int)((tw >> (8 * k)) & 0xffu) - (int)((pw >> (8 * k)) & 0xffu);
       ssd += (uint32_t)(df[k] * df[k]);
     }
-    const uint32_t e = la_row_sum(ssd) >> 6;  // (<= 65 025)
+    const uint32_t e = row_reduce(ssd, OpSum()) >> 6;  // (<= 65 025)
     if (sub_live && l16 == 0) *rec = ((uint32_t)mvx & 0xffu) | (((uint32_t)mvy & 0xffu) << 8) | (e << 16);
 #pragma unroll
     for (int k = 0; k < 4; k++) {
@@ -280,16 +263,16 @@ __global__ __launch_bounds__(256) void k_tf_chroma(const TfArgs A) {
   if (bx >= A.bw8 || by >= A.bh8) return;
   const int cw = A.w >> 1, ch = A.h >> 1;
   const int cs = tg->cs[1], ds = tg->ds[1];
-  const sse_gptr cur = (sse_gptr)tg->cur[pl] + (long long)(4 * by) * cs + 4 * bx;
+  const gcptr cur = (gcptr)tg->cur[pl] + (long long)(4 * by) * cs + 4 * bx;
   uint32_t tw[4], num[16], den[16];
 #pragma unroll
   for (int j = 0; j < 4; j++) {
-    tw[j] = sse_ld4(cur + (long long)j * cs);
+    tw[j] = g_ld4(cur + (long long)j * cs);
 #pragma unroll
     for (int k = 0; k < 4; k++) num[4 * j + k] = 256u * ((tw[j] >> (8 * k)) & 0xffu), den[4 * j + k] = 256u;
   }
   for (int r = 0; r < A.nrefs; r++) {
-    const sse_gptr ref = (sse_gptr)tg->ref[r][pl];
+    const gcptr ref = (gcptr)tg->ref[r][pl];
     if (!tg->ref[r][0]) continue;
     const int rs = tg->rs[r][1];
     const uint32_t rec = A.recs[(((size_t)z * A.nrefs + r) * A.bh8 + by) * A.bw8 + bx];
@@ -300,10 +283,10 @@ __global__ __launch_bounds__(256) void k_tf_chroma(const TfArgs A) {
     uint32_t pw[4], a = 0, b = 0;
 #pragma unroll
     for (int j = 0; j < 5; j++) {
-      const sse_gptr row = ref + (long long)min(max(iy + j, 0), ch - 1) * rs;
+      const gcptr row = ref + (long long)min(max(iy + j, 0), ch - 1) * rs;
       uint32_t lo, ex;
       if (inside) {
-        lo = sse_ld4(row + ix), ex = row[ix + 4];
+        lo = g_ld4(row + ix), ex = row[ix + 4];
       } else {
         lo = 0;
 #pragma unroll
@@ -417,8 +400,7 @@ int thor_tf_i420(thor_tf_t *t, const thor_yuv_planes_t *cur, const thor_yuv_plan
   std::vector<LaPair> pairs((size_t)n * nrefs);
   for (int i = 0; i < n; i++) {
     const thor_yuv_planes_t &c = cur[i], &d = dst[i];
-    if (!c.y || !c.u || !c.v || !d.y || !d.u || !d.v) return THOR_ERR_ARG;
-    if (c.stride_y < W || c.stride_c < (W >> 1) || d.stride_y < W || d.stride_c < (W >> 1)) return THOR_ERR_ARG;
+    if (!planes_ok(c, W) || !planes_ok(d, W)) return THOR_ERR_ARG;
     if (d.y == c.y || d.u == c.u || d.v == c.v) return THOR_ERR_ARG;  // not in place
     TfTarget &g = tg[i];
     memset(&g, 0, sizeof(g));
@@ -428,13 +410,12 @@ int thor_tf_i420(thor_tf_t *t, const thor_yuv_planes_t *cur, const thor_yuv_plan
     for (int r = 0; r < nrefs; r++) {
       const thor_yuv_planes_t &f = refs[(size_t)i * nrefs + r];
       LaPair &p = pairs[(size_t)i * nrefs + r];
-      p.cur = c.y, p.cs = c.stride_y, p.ref = nullptr, p.rs = 0;
+      la_fill_pair(p, c, &f);
       if (!f.y) continue;  // absent
-      if (!f.u || !f.v || f.stride_y < W || f.stride_c < (W >> 1)) return THOR_ERR_ARG;
+      if (!planes_ok(f, W)) return THOR_ERR_ARG;
       if (d.y == f.y || d.u == f.u || d.v == f.v) return THOR_ERR_ARG;
       g.ref[r][0] = f.y, g.ref[r][1] = f.u, g.ref[r][2] = f.v;
       g.rs[r][0] = f.stride_y, g.rs[r][1] = f.stride_c;
-      p.ref = f.y, p.rs = f.stride_y;
     }
   }
   HIPCHK(hipSetDevice(t->device));
@@ -451,16 +432,13 @@ int thor_tf_i420(thor_tf_t *t, const thor_yuv_planes_t *cur, const thor_yuv_plan
   uint32_t *const recs = mv_dev ? (uint32_t *)mv_dev : t->recs;
   const dim3 gl((unsigned)((W + TF_TILE_W - 1) / TF_TILE_W), (unsigned)((H + TF_TILE_H - 1) / TF_TILE_H), 1);
   const dim3 gc((unsigned)((A.bw8 + TF_CBX - 1) / TF_CBX), (unsigned)((A.bh8 + TF_CBY - 1) / TF_CBY), 1);
-  for (int i0 = 0; i0 < n; i0 += TF_INL) {
-    const int m = n - i0 < TF_INL ? n - i0 : TF_INL;
+  return launch_batches(n, TF_INL, [&](int i0, int m) {
     memcpy(A.inl, tg.data() + i0, (size_t)m * sizeof(TfTarget));
     A.recs = recs + (size_t)i0 * nrefs * A.bw8 * A.bh8;
     A.la = (const uint2 *)t->la + (size_t)i0 * nrefs * A.lbw * A.lbh;
     k_tf_luma<<<dim3(gl.x, gl.y, (unsigned)m), 256, 0, st>>>(A);
     k_tf_chroma<<<dim3(gc.x, gc.y, (unsigned)(2 * m)), 256, 0, st>>>(A);
-  }
-  if (hipGetLastError() != hipSuccess) return THOR_ERR_HIP;
-  return THOR_OK;
+  });
 }
 
 }  // extern "C"

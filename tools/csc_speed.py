@@ -15,33 +15,12 @@ repetitions; median, minimum and maximum are reported.  No GPU, no numbers.
     python tools/csc_speed.py --out profiles/csc_speed.json
 """
 import argparse
-import json
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-
-def timed(torch, fn, launches, reps, warmup=2):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(launches):
-            fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b) / launches)
-    ms.sort()
-    return ms
-
-
-def rates(nbytes, ms):
-    gb = [nbytes / (t * 1e-3) / 1e9 for t in ms]  # ms ascending -> rates descending
-    return {"ms_median": ms[len(ms) // 2], "gbps_median": gb[len(gb) // 2], "gbps_min": gb[-1], "gbps_max": gb[0]}
+from speed_common import rates, timed, write_result  # noqa: E402
 
 
 def torch_to_rgb(torch, frames, W, H, bilinear, as_float, hwc):
@@ -165,12 +144,7 @@ def main():
                                                   case["vs_torch"], case["vs_copy"]), flush=True)
         del rgb
         torch.cuda.empty_cache()
-    line = json.dumps(res)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
-    print(line)
+    write_result(res, a.out)
 
 
 if __name__ == "__main__":

@@ -23,40 +23,16 @@ the child), and the parent gives up on the child after their sum.
     python tools/lookahead_speed.py --out profiles/lookahead_speed.json
 """
 import argparse
-import json
 import os
-import signal
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+from speed_common import run_worker, timed_step, write_result  # noqa: E402
+
 STEPS = ("lookahead", "lookahead_sums_only", "ssim", "copy")
-
-
-def timed(torch, fn, launches, reps, warmup=2):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(launches):
-            fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b) / launches)
-    ms.sort()
-    return ms
-
-
-def rates(nbytes, ms):
-    gb = [nbytes / (t * 1e-3) / 1e9 for t in ms]  # ms ascending -> rates descending
-    return {"ms_median": ms[len(ms) // 2], "ms_min": ms[0], "ms_max": ms[-1], "gbps_median": gb[len(gb) // 2],
-            "gbps_min": gb[-1], "gbps_max": gb[0]}
 
 
 def worker(a):
@@ -110,9 +86,7 @@ def worker(a):
     res = {"width": W, "height": H, "n": n, "launches": a.launches, "reps": a.reps, "bytes_per_call": la_bytes,
            "ssim_bytes_per_call": ssim_bytes, "blocks_per_frame": bw * bh, "device": torch.cuda.get_device_name(0)}
     for name, fn, nbytes in zip(STEPS, (lookahead, lookahead_sums_only, ssim, copy), (la_bytes, la_bytes, ssim_bytes, la_bytes)):
-        signal.alarm(a.step_seconds)  # this step's own limit: the alarm ends the process
-        res[name] = rates(nbytes, timed(torch, fn, a.launches, a.reps))
-        signal.alarm(0)
+        res[name] = timed_step(torch, fn, nbytes, a, ms_range=True)
         print("%-20s %8.1f GB/s (%.1f..%.1f)  %.3f ms per call (%.3f..%.3f)" % (
             name, res[name]["gbps_median"], res[name]["gbps_min"], res[name]["gbps_max"], res[name]["ms_median"],
             res[name]["ms_min"], res[name]["ms_max"]), flush=True)
@@ -146,12 +120,7 @@ def worker(a):
     res["ratio_min_over_intra"] = float(got_s[:, 2].sum()) / float(got_s[:, 0].sum())
     print("pairs %s of both results equal the model; sum min / sum intra = %.3f" % (res["checked_pairs"], res["ratio_min_over_intra"]),
           flush=True)
-    line = json.dumps(res)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
-    print(line)
+    write_result(res, a.out)
 
 
 def main():
@@ -169,13 +138,7 @@ def main():
         return worker(a)
     # set-up (torch import, 1.6 GB of frames), the steps, the model on two 4K pairs
     limit = 300 + len(STEPS) * a.step_seconds
-    try:
-        rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker"] + sys.argv[1:], timeout=limit).returncode
-    except subprocess.TimeoutExpired:
-        raise SystemExit("lookahead_speed: the measurement did not finish in %d s" % limit)
-    if rc == -signal.SIGALRM:
-        raise SystemExit("lookahead_speed: a step ran past its %d s limit" % a.step_seconds)
-    raise SystemExit(rc)
+    run_worker("lookahead_speed", __file__, a.step_seconds, limit)
 
 
 if __name__ == "__main__":

@@ -18,7 +18,6 @@ last frame of every result are compared with the Python model of the contract
     python tools/scale_speed.py --out profiles/scale_speed.json
 """
 import argparse
-import json
 import os
 import sys
 
@@ -26,27 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-
-def timed(torch, fn, launches, reps, warmup=2):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(launches):
-            fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b) / launches)
-    ms.sort()
-    return ms
-
-
-def rates(nbytes, ms):
-    gb = [nbytes / (t * 1e-3) / 1e9 for t in ms]  # ms ascending -> rates descending
-    return {"ms_median": ms[len(ms) // 2], "gbps_median": gb[len(gb) // 2], "gbps_min": gb[-1], "gbps_max": gb[0]}
+from speed_common import rates, timed, write_result  # noqa: E402
 
 
 def torch_scale(torch, frames, sw, sh, dw, dh, mode):
@@ -128,12 +107,7 @@ def main():
                   flush=True)
             torch.cuda.empty_cache()
         del out
-    line = json.dumps(res)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
-    print(line)
+    write_result(res, a.out)
 
 
 if __name__ == "__main__":

@@ -19,38 +19,15 @@ ends the child), and the parent gives up on the child after their sum.
     python tools/ssim_speed.py --out profiles/ssim_speed.json
 """
 import argparse
-import json
 import os
-import signal
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from speed_common import run_worker, timed_step, write_result  # noqa: E402
+
 STEPS = ("ssim", "sse", "copy")
-
-
-def timed(torch, fn, launches, reps, warmup=2):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(launches):
-            fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b) / launches)
-    ms.sort()
-    return ms
-
-
-def rates(nbytes, ms):
-    gb = [nbytes / (t * 1e-3) / 1e9 for t in ms]  # ms ascending -> rates descending
-    return {"ms_median": ms[len(ms) // 2], "gbps_median": gb[len(gb) // 2], "gbps_min": gb[-1], "gbps_max": gb[0]}
 
 
 def worker(a):
@@ -89,9 +66,7 @@ def worker(a):
     res = {"width": W, "height": H, "n": n, "launches": a.launches, "reps": a.reps, "bytes_per_call": nbytes,
            "device": torch.cuda.get_device_name(0)}
     for name, fn in zip(STEPS, (ssim, sse, copy)):
-        signal.alarm(a.step_seconds)  # this step's own limit: the alarm ends the process
-        res[name] = rates(nbytes, timed(torch, fn, a.launches, a.reps))
-        signal.alarm(0)
+        res[name] = timed_step(torch, fn, nbytes, a)
         print("%-5s %8.1f GB/s (%.1f..%.1f)  %.3f ms per call" % (
             name, res[name]["gbps_median"], res[name]["gbps_min"], res[name]["gbps_max"], res[name]["ms_median"]),
             flush=True)
@@ -102,12 +77,7 @@ def worker(a):
     res["ssim_vs_sse"] = res["ssim"]["gbps_median"] / res["sse"]["gbps_median"]
     res["ssim_vs_copy"] = res["ssim"]["gbps_median"] / res["copy"]["gbps_median"]
     print("ssim: %.2f of sse, %.2f of copy" % (res["ssim_vs_sse"], res["ssim_vs_copy"]), flush=True)
-    line = json.dumps(res)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
-    print(line)
+    write_result(res, a.out)
 
 
 def main():
@@ -125,13 +95,7 @@ def main():
         return worker(a)
     # set-up (torch import, 2.4 GB of frames) + the three steps
     limit = 180 + len(STEPS) * a.step_seconds
-    try:
-        rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker"] + sys.argv[1:], timeout=limit).returncode
-    except subprocess.TimeoutExpired:
-        raise SystemExit("ssim_speed: the measurement did not finish in %d s" % limit)
-    if rc == -signal.SIGALRM:
-        raise SystemExit("ssim_speed: a step ran past its %d s limit" % a.step_seconds)
-    raise SystemExit(rc)
+    run_worker("ssim_speed", __file__, a.step_seconds, limit)
 
 
 if __name__ == "__main__":

@@ -25,40 +25,16 @@ the child), and the parent gives up on the child after their sum.
     python tools/tf_speed.py --out profiles/tf_speed.json
 """
 import argparse
-import json
 import os
-import signal
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+from speed_common import run_worker, timed_step, write_result  # noqa: E402
+
 STEPS = ("filter", "filter_no_records", "lookahead", "copy")
-
-
-def timed(torch, fn, launches, reps, warmup=2):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(launches):
-            fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b) / launches)
-    ms.sort()
-    return ms
-
-
-def rates(nbytes, ms):
-    gb = [nbytes / (t * 1e-3) / 1e9 for t in ms]  # ms ascending -> rates descending
-    return {"ms_median": ms[len(ms) // 2], "ms_min": ms[0], "ms_max": ms[-1], "gbps_median": gb[len(gb) // 2],
-            "gbps_min": gb[-1], "gbps_max": gb[0]}
 
 
 def worker(a):
@@ -129,9 +105,7 @@ def worker(a):
            "device": torch.cuda.get_device_name(0)}
     for name, fn, nbytes in zip(STEPS, (filt, filt_no_records, lookahead, copy),
                                 (tf_bytes, tf_bytes, 2 * n * nrefs * W * H, tf_bytes)):
-        signal.alarm(a.step_seconds)  # this step's own limit: the alarm ends the process
-        res[name] = rates(nbytes, timed(torch, fn, a.launches, a.reps))
-        signal.alarm(0)
+        res[name] = timed_step(torch, fn, nbytes, a, ms_range=True)
         print("%-20s %8.1f GB/s (%.1f..%.1f)  %.3f ms per call (%.3f..%.3f)" % (
             name, res[name]["gbps_median"], res[name]["gbps_min"], res[name]["gbps_max"], res[name]["ms_median"],
             res[name]["ms_min"], res[name]["ms_max"]), flush=True)
@@ -162,12 +136,7 @@ def worker(a):
     res["pixels_changed"] = float((got != host[R:R + n]).mean())
     print("targets %s equal the model; %.3f of the bytes changed" % (res["checked_targets"], res["pixels_changed"]), flush=True)
     tf.close()
-    line = json.dumps(res)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
-    print(line)
+    write_result(res, a.out)
 
 
 def main():
@@ -188,13 +157,7 @@ def main():
         return worker(a)
     # set-up (torch import, the frames), the steps, the model on the checked targets
     limit = 300 + len(STEPS) * a.step_seconds + 240 * a.check
-    try:
-        rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker"] + sys.argv[1:], timeout=limit).returncode
-    except subprocess.TimeoutExpired:
-        raise SystemExit("tf_speed: the measurement did not finish in %d s" % limit)
-    if rc == -signal.SIGALRM:
-        raise SystemExit("tf_speed: a step ran past its %d s limit" % a.step_seconds)
-    raise SystemExit(rc)
+    run_worker("tf_speed", __file__, a.step_seconds, limit)
 
 
 if __name__ == "__main__":
